@@ -5,12 +5,17 @@
 RoBERTa-base (random weights, frozen, the shipped configs) -> text_emb / img_emb -> one rollout timestep (actor + critic + reward
 no-grad forwards, finetune/ppo.py:844-883) -> one update minibatch (actor fwd/bwd/AdamW + critic fwd/bwd/AdamW with the fused PPO
 loss, finetune/ppo.py:518-587, dropout on as under model.train()), 32 items x 2 tags per GPU, everything resident in HBM.
-`head_only_steps_per_sec` (top level): the same rollout + update on PRE-EXTRACTED features, which is what the reference's own PPO
+`head_only_steps_per_sec` (top level, --full): the same rollout + update on PRE-EXTRACTED features, which is what the reference's own PPO
 loop runs (it reads clean_feat.h5, finetune/ppo.py:115-148) -- rounds 1-2 reported that one as `value`.
 
     python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run, one rank per GPU)
+                    [--dump-outputs DIR] [--full]
 
-Prints ONE JSON line on rank 0.  `roofline`: the kernel signature with the most device time in the `value` loop (the ViT FFN-1
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the --steps steps of the `value` loop, writes that loop's
+outputs when --dump-outputs DIR is given and prints the line: `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`
+and the configuration.  Everything below is measured only under --full.
+
+--full: `roofline`: the kernel signature with the most device time in the `value` loop (the ViT FFN-1
 GEMM of the 256 x 256 MFMA kernel), HIP events on its launch stream inside the timed region; `roofline_hbm`: the dominant
 HBM-bound kernel of the head (fused out_layer.fc1 weight gradient + AdamW).  Single-GPU extras (top-level scalars + `config`):
 dual-encoder forward and forward+backward (MFMA issue fraction), BASELINE configs[1] (stage-1 pointwise at 32 x 20 tags) with
@@ -54,6 +59,14 @@ def parse():
     ap.add_argument("--no-extras", action="store_true", help="skip the single-GPU extras (encoder fwd / fwd+bwd, stage-1 figures)")
     ap.add_argument("--no-stage1", action="store_true", help="skip the BASELINE configs[1] figures (stage-1 step at 32 x 20 tags)")
     ap.add_argument("--no-graph", action="store_true", help="skip the HIP-graph replay of the head-only step (head_only_graph)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: the head-only loop and its HIP-graph replay next to the "
+                         "composed `value` loop, per-kernel roofline figures, the single-GPU extras, BASELINE configs[1] / [4] and the "
+                         "CPU baseline (the --no-* options select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step (the PPO metrics, the rollout "
+                         "record, the extracted features) as DIR/<name>.npy, float32, at most 64 MB in all (a fixed seeded sample "
+                         "of each array when larger)")
     ap.add_argument("--serial-streams", action="store_true",
                     help="one HIP stream for the whole PPO step (LR2_PPO_STREAMS=0): every launch runs alone, so a kernel trace "
                          "of this command shows exclusive per-kernel durations; the default schedule runs the critic beside the actor")
@@ -103,6 +116,25 @@ def _pmc(key):
             return json.load(f)["by_bench_label"].get(key)
     except (OSError, KeyError, ValueError):
         return None
+
+
+DUMP_MAX_ELEMENTS = 16_000_000 - 4096       # float32: 64 MB in all, with room for the .npy headers
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as `path/<name>.npy` in float32.  When the arrays together exceed DUMP_MAX_ELEMENTS, each one is
+    replaced by the same fraction of its elements, picked by a fixed seed and kept in index order (flattened): a run with the
+    same arguments writes the same positions, so that two builds can be compared output for output."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = sum(t.numel() for t in arrays.values())
+    for name, t in arrays.items():
+        x = t.detach().to(torch.float32).cpu()
+        if total > DUMP_MAX_ELEMENTS:
+            k = max(1, x.numel() * DUMP_MAX_ELEMENTS // total)
+            idx = torch.randperm(x.numel(), generator=torch.Generator().manual_seed(0))[:k].sort().values
+            x = x.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), x.numpy())
 
 
 def launcher_command(gpus: int, argv, script: str, port: int):
@@ -222,11 +254,26 @@ def main():
              torch.randn(a.batch, 16, 768, device=dev, generator=g),          # shared by the tags of an item
              torch.randint(0, 3, (a.batch, a.tags), device=dev, generator=g)) for _ in range(n_batches)]
 
+    last_rec = []                                  # --dump-outputs: the rollout record of the latest PPO step
+
     def ppo_step(text, img, tgts):
         model.eval()
         rec = ppo.rollout_step(model, reward, text, img, tgts)
+        if a.dump_outputs is not None:
+            last_rec[:] = [rec]
         model.train()
         return ppo.update_minibatch(margs, model, opt, copt, rec, dp)
+
+    def write_outputs(metrics, features):
+        """--dump-outputs, rank 0, right after the timed steps of the `value` loop: what its last step handed back."""
+        if a.dump_outputs is None or rank != 0:
+            return
+        _, next_state, scores, rewards, value, text, img, _ = last_rec[0]
+        arrays = {"ppo_metrics": metrics, "rollout_scores": scores, "rollout_rewards": rewards, "rollout_value": value,
+                  "rollout_next_state": next_state}
+        if features:
+            arrays.update(text_emb=text, img_emb=img)
+        dump_outputs(a.dump_outputs, arrays)
 
     def step(i):
         return ppo_step(*data[i % n_batches])
@@ -244,55 +291,59 @@ def main():
         return float(t.item())
 
     # ================= [A] head-only loop (pre-extracted features: the reference's real PPO loop) =================
-    # Per-kernel HIP events: every GEMM / AdamW signature during the LAST warm-up step (ranking, `top_ms_per_step`); inside the
-    # timed region only the dominant signature is bracketed, so that the measurement does not slow the thing it measures (two
-    # event records per launch on ~120 launches made the step host-bound).
-    survey = {}
-    for i in range(a.warmup):
-        last = (i == a.warmup - 1) and not a.no_profile
-        if last:
-            fence()
-            ops.profile_start()
-            with exclusive_launches():
+    # --full, or the `value` loop of --no-online.  Per-kernel HIP events (--full): every GEMM / AdamW signature during the LAST
+    # warm-up step (ranking, `top_ms_per_step`); inside the timed region only the dominant signature is bracketed, so that the
+    # measurement does not slow the thing it measures (two event records per launch on ~120 launches made the step host-bound).
+    survey, prof, prof_excl, EXCL = {}, {}, {}, 4
+    host_enqueue_ms = head_dt = one_stream_ms = graphed = None
+    profile = a.full and not a.no_profile
+    if a.full or a.no_online:
+        for i in range(a.warmup):
+            last = (i == a.warmup - 1) and profile
+            if last:
+                fence()
+                ops.profile_start()
+                with exclusive_launches():
+                    m = step(i)
+                survey = ops.profile_stop()
+            else:
                 m = step(i)
-            survey = ops.profile_stop()
-        else:
-            m = step(i)
-    fence()
-    # Host cost of enqueueing one step, measured on an EMPTY launch queue (3 steps after a synchronise): inside the timed loop
-    # the host runs ahead until the HIP launch queue is full and then spins on back-pressure.
-    t0 = time.perf_counter()
-    for i in range(3):
-        step(i)
-    host_enqueue_ms = (time.perf_counter() - t0) / 3 * 1e3
-    fence()
-    dominant = max(survey.items(), key=lambda kv: kv[1]["ms"])[0] if survey else None
-    if not a.no_profile:
-        ops.profile_start(only=None if dominant is None else [dominant])
-    t0 = time.perf_counter()
-    for i in range(a.steps):
-        m = step(a.warmup + i)
-    fence()
-    head_dt = time.perf_counter() - t0
-    prof = ops.profile_stop() if not a.no_profile else {}
-    if not torch.isfinite(m).all():
-        raise SystemExit("bench: non-finite PPO metrics")
-    # the dominant signature again, each launch ALONE on the chip: EXCL extra steps on one stream right after the timed region
-    prof_excl, EXCL = {}, 4
-    if prof and two_streams:
-        with exclusive_launches():
-            step(a.warmup + a.steps)
+        fence()
+        if a.full:
+            # Host cost of enqueueing one step, measured on an EMPTY launch queue (3 steps after a synchronise): inside the timed
+            # loop the host runs ahead until the HIP launch queue is full and then spins on back-pressure.
+            t0 = time.perf_counter()
+            for i in range(3):
+                step(i)
+            host_enqueue_ms = (time.perf_counter() - t0) / 3 * 1e3
             fence()
-            ops.profile_start(only=[dominant])
-            for i in range(EXCL):
-                step(a.warmup + a.steps + 1 + i)
-            fence()
-            prof_excl = ops.profile_stop()
-    head_dt = max_over_ranks(head_dt)
+        dominant = max(survey.items(), key=lambda kv: kv[1]["ms"])[0] if survey else None
+        if profile:
+            ops.profile_start(only=None if dominant is None else [dominant])
+        t0 = time.perf_counter()
+        for i in range(a.steps):
+            m = step(a.warmup + i)
+        fence()
+        head_dt = time.perf_counter() - t0
+        prof = ops.profile_stop() if profile else {}
+        if not torch.isfinite(m).all():
+            raise SystemExit("bench: non-finite PPO metrics")
+        if a.no_online:
+            write_outputs(m, features=False)
+        # the dominant signature again, each launch ALONE on the chip: EXCL extra steps on one stream right after the timed region
+        if prof and two_streams:
+            with exclusive_launches():
+                step(a.warmup + a.steps)
+                fence()
+                ops.profile_start(only=[dominant])
+                for i in range(EXCL):
+                    step(a.warmup + a.steps + 1 + i)
+                fence()
+                prof_excl = ops.profile_stop()
+        head_dt = max_over_ranks(head_dt)
     # the ONE-stream schedule, eager: what world > 1 runs by default, so that the N = 1 -> N = 2 step of a scaling
     # curve can be read against the same schedule at N = 1
-    one_stream_ms = None
-    if two_streams:
+    if a.full and two_streams:
         with exclusive_launches():
             step(0)
             fence()
@@ -304,8 +355,7 @@ def main():
 
     # the same head-only step captured in a HIP graph (ppo.GraphedPPOStep: dropout seeds and learning rates in device memory),
     # two-stream schedule and one-stream schedule: host cost of one replay on an empty queue, and the step time
-    graphed = None
-    if world == 1 and not a.no_graph:
+    if a.full and world == 1 and not a.no_graph:
         def graph_measure():
             gstep = ppo.GraphedPPOStep(margs, model, reward, opt, copt)
             for i in range(3):                     # eager (sizes the workspaces), capture + replay, replay
@@ -349,9 +399,9 @@ def main():
             return ppo_step(text, img, tg)
 
         osurvey = {}
-        nw = max(2, min(a.warmup, 3))
+        nw = max(2, a.warmup)
         for i in range(nw):
-            if i == nw - 1 and not a.no_profile:
+            if i == nw - 1 and profile:
                 fence()
                 ops.profile_start()
                 with exclusive_launches():
@@ -372,6 +422,7 @@ def main():
         fx.text.embedding.check_ids()
         if not torch.isfinite(m2).all():
             raise SystemExit("bench: non-finite PPO metrics in the composed loop")
+        write_outputs(m2, features=True)
         online = {"dt": max_over_ranks(dt), "prof": oprof, "survey": osurvey, "dominant": odom}
 
     if rank != 0:
@@ -381,7 +432,7 @@ def main():
 
     sched = ("critic forward / backward / optimizer step on a second HIP stream beside the actor's" if two_streams
              else "one HIP stream")
-    head_rate = world * a.steps / head_dt
+    head_rate = None if head_dt is None else world * a.steps / head_dt
     if online is not None:
         dt = online["dt"]
         value, ms_per_step = world * a.steps / dt, dt / a.steps * 1e3
@@ -401,13 +452,13 @@ def main():
         "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "f32 (GEMMs: split-bf16 x3 on MFMA, fp32 accumulate)" if a.passes == 3 else "bf16 inputs, fp32 accumulate (1 pass)",
         "data": "synthetic",
-        "head_only_steps_per_sec": round(head_rate, 3), "head_only_ms_per_step": round(head_dt / a.steps * 1e3, 3),
-        "head_only_one_stream_ms": None if one_stream_ms is None else round(one_stream_ms, 3),
-        "head_only_graph": graphed,
         "config": {"workload": workload, "batch_per_gpu": a.batch, "tags": a.tags, "global_batch": a.batch * world,
                    "parallelism": f"dp{world}", "schedule": sched, "items_per_sec": round(value * a.batch, 1),
                    "algorithmic_tflop_per_step": {"head": 3.44, "dual_encoder_forward": 18.96} if (a.batch, a.tags) == (32, 2) else None},
     }
+    if a.full:
+        out.update(head_only_steps_per_sec=round(head_rate, 3), head_only_ms_per_step=round(head_dt / a.steps * 1e3, 3),
+                   head_only_one_stream_ms=None if one_stream_ms is None else round(one_stream_ms, 3), head_only_graph=graphed)
     # ---- roofline of the `value` loop's dominant kernel signature (measured inside its timed region; the encoder launches run
     # alone on the main stream: the side stream only carries the critic inside the PPO step) ----
     if online is not None and online["prof"]:
@@ -459,7 +510,7 @@ def main():
             out["roofline"] = rl
 
     # ================= [C] single-GPU extras =================
-    if world == 1 and online is not None and not a.no_extras:
+    if a.full and world == 1 and online is not None and not a.no_extras:
         import encoder_bench
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         # the extractor alone, same inputs (HIP events on the launch stream), for the MFMA-utilisation figure
@@ -772,7 +823,7 @@ def main():
             torch.cuda.empty_cache()
         del fx, raw
     # ================= [D] CPU baseline: the oracle on this box's host cores, bounded sample =================
-    if world == 1 and not a.no_cpu_baseline:
+    if a.full and world == 1 and not a.no_cpu_baseline:
         del model, reward, opt, copt, data
         torch.cuda.empty_cache()
         from oracle import cpu_baseline

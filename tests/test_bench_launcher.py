@@ -73,3 +73,21 @@ def test_bench_gpus_2_on_a_box_without_gpu_exits_nonzero_instead_of_reporting_on
         assert json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])["n_gpus"] == 2
     else:
         assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+
+
+def test_dump_outputs_writes_float32_npy_and_samples_above_64_mb(tmp_path, monkeypatch):
+    """--dump-outputs: one float32 .npy per array; above the cap every array keeps the same fixed, seeded share of its elements."""
+    import numpy as np
+    import torch
+    small = {"ppo_metrics": torch.arange(10, dtype=torch.float32), "rollout_next_state": torch.arange(8).view(2, 4)}
+    bench.dump_outputs(str(tmp_path / "a"), small)
+    m = np.load(tmp_path / "a" / "ppo_metrics.npy")
+    s = np.load(tmp_path / "a" / "rollout_next_state.npy")
+    assert m.dtype == np.float32 and s.dtype == np.float32 and s.shape == (2, 4) and (m == np.arange(10)).all()
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMENTS", 1000)
+    big = {"x": torch.randn(3000), "y": torch.randn(1000)}
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    x, y = np.load(tmp_path / "b" / "x.npy"), np.load(tmp_path / "b" / "y.npy")
+    assert x.size + y.size <= 1000 and x.size == 750 and y.size == 250
+    assert np.isin(x, big["x"].numpy()).all() and (np.load(tmp_path / "c" / "x.npy") == x).all()

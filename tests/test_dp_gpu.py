@@ -33,8 +33,9 @@ def test_bench_gpus_2_starts_two_ranks_and_reports_them(dev):
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(LR2_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-extras",
-                        "--no-cpu-baseline", "--no-graph", "--no-profile"], capture_output=True, text=True, timeout=600, env=env)
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full",
+                        "--no-extras", "--no-cpu-baseline", "--no-graph", "--no-profile"], capture_output=True, text=True, timeout=600,
+                       env=env)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1

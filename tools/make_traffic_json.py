@@ -59,7 +59,7 @@ if os.path.exists(_ef) and os.path.exists(_ew):
         rec.update(read_bytes=int(2 * fetch), write_bytes=int(write), hbm_bytes=int(2 * fetch + write), traffic_launches=r["launches"])
 print(json.dumps({
     "_method": "tools/profile_round.sh " + tag + ": rocprofv3 --kernel-trace --pmc FETCH_SIZE (pass 1) / --pmc WRITE_SIZE (pass 2) on "
-               "`python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-online --no-profile` (head-only PPO steps), summarised per dispatch signature by "
+               "`python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-online --no-profile` (head-only PPO steps), summarised per dispatch signature by "
                "tools/rocprof_summary.py; counters are KiB; read bytes = 2 x FETCH_SIZE (gfx950, 16-B/lane streaming reads), WRITE_SIZE as "
                "is.  kernel_trace_* come from the `--serial-streams` kernel-trace pass of the SAME gpurun call (same box, 13 PPO steps on one "
                "HIP stream: exclusive per-launch durations).  mfma_busy / effective_clock_ghz: SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 "
