@@ -55,89 +55,8 @@ __global__ __launch_bounds__(256) void quant_mxfp8_kernel(const float* __restric
   }
 }
 
-// ---- product: 4 waves (2 x 2) per workgroup, tile 128 x 128, wave tile 64 x 64 = 4 x 4 instruction tiles, K step 128 ----
-// Fragments come straight from global memory (a lane's operand is 2 x 16 contiguous bytes of a row; the four lanes of a row read
-// one 128-byte line between them): the L1 / L2 hit rate does the staging an LDS ring would do.  The next K step's fragments are
-// requested before this step's 16 instructions.
-struct Frags {
-  v8i_t a[4], b[4];
-  int sa[4], sb[4];
-};
-
-__device__ __forceinline__ void load_frags(const Mx8Params& p, Frags& f, const uint8_t* const (&arow)[4], const uint8_t* const (&brow)[4],
-                                           const uint8_t* const (&asrow)[4], const uint8_t* const (&bsrow)[4], int k0, int q) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const v4i_t a0 = *reinterpret_cast<const v4i_t*>(arow[i] + k0 + 16 * q);
-    const v4i_t a1 = *reinterpret_cast<const v4i_t*>(arow[i] + k0 + 64 + 16 * q);
-    f.a[i] = v8i_t{a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
-    const v4i_t b0 = *reinterpret_cast<const v4i_t*>(brow[i] + k0 + 16 * q);
-    const v4i_t b1 = *reinterpret_cast<const v4i_t*>(brow[i] + k0 + 64 + 16 * q);
-    f.b[i] = v8i_t{b0[0], b0[1], b0[2], b0[3], b1[0], b1[1], b1[2], b1[3]};
-    f.sa[i] = (int)asrow[i][(k0 >> 5) + q];
-    f.sb[i] = (int)bsrow[i][(k0 >> 5) + q];
-  }
-}
-
-__global__ __launch_bounds__(256) void gemm_mxfp8_kernel(Mx8Params p) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int wr = wave >> 1, wc = wave & 1;
-  const int tiles_n = p.N / 128;
-  // XCD-aware order is not needed for correctness; keep neighbouring tiles of one row on one XCD's L2 by walking N fastest
-  const int tm = blockIdx.x / tiles_n, tn = blockIdx.x % tiles_n;
-  const int m0 = tm * 128 + wr * 64, n0 = tn * 128 + wc * 64;
-  const int r16 = lane & 15, q = lane >> 4;
-  const uint8_t* arow[4];
-  const uint8_t* brow[4];
-  const uint8_t* asrow[4];
-  const uint8_t* bsrow[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    int m = m0 + 16 * i + r16;
-    if (m >= p.M) m = p.M - 1;                             // ragged M: clamped reads, masked stores
-    const int n = n0 + 16 * i + r16;
-    arow[i] = p.aq + (size_t)m * p.K;
-    brow[i] = p.bq + (size_t)n * p.K;
-    asrow[i] = p.as + (size_t)m * (p.K / 32);
-    bsrow[i] = p.bs + (size_t)n * (p.K / 32);
-  }
-  f32x4_t acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-  Frags cur, nxt;
-  load_frags(p, cur, arow, brow, asrow, bsrow, 0, q);
-  for (int k0 = 0; k0 < p.K; k0 += 128) {
-    if (k0 + 128 < p.K) load_frags(p, nxt, arow, brow, asrow, bsrow, k0 + 128, q);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(cur.a[i], cur.b[j], acc[i][j], 0, 0, 0, cur.sa[i], 0, cur.sb[j]);
-    if (k0 + 128 < p.K) cur = nxt;
-  }
-  // epilogue: acc[i][j][r] = C[m0 + 16 i + 4 q + r][n0 + 16 j + r16]
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int n = n0 + 16 * j + r16;
-    const float bj = p.bias ? p.bias[n] : 0.0f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int m = m0 + 16 * i + 4 * q + r;
-        if (m < p.M) {
-          float v = acc[i][j][r] + bj;
-          if (p.act == 1) v = gelu_erf(v);
-          if (p.resid) v += p.resid[(size_t)m * p.ld_resid + n];
-          p.out[(size_t)m * p.ld_out + n] = v;
-        }
-      }
-  }
-}
-
-// ---- the same product with the operand tiles staged through LDS (two stages of 128 rows x 128 bytes per operand = 64 KiB) ----
+// ---- product: 4 waves (2 x 2) per workgroup, tile 128 x 128, wave tile 64 x 64 = 4 x 4 instruction tiles, K step 128, operand
+// tiles staged through LDS (two stages of 128 rows x 128 bytes per operand = 64 KiB) ----
 // A 16-byte chunk c of tile row r lives at r * 128 + ((c ^ (r & 7)) << 4): the 16 lanes of a fragment read (rows r .. r + 15, one
 // chunk column) then hit 8 different 16-byte bank groups twice instead of one group 16 times.  Each thread moves four chunks of A
 // and four of B per K step: requested from global memory before the step's matrix instructions, written to the other stage after.
@@ -325,25 +244,12 @@ extern "C" int lr2_gemm_mxfp8(const void* a_q, const void* a_scales, const void*
               (const float*)bias, (const float*)resid, M, N, K, ld_out, ld_resid, act, (uint8_t*)out_q, (uint8_t*)out_scales,
               (bf16_t*)out_hi, (size_t)out_lo_off, ld_planes};
   // Large products (the encoders' token products at M >= 1e4 rows): the 256 x 256 LDS-DMA ring of gemm256_mx.hip when its
-  // one-workgroup-per-CU rounds are well filled; LR2_FP8_256=0 keeps everything on the 128 x 128 kernel (A/B).
-  {
-    static int env256 = -1;
-    if (env256 < 0) {
-      const char* e2 = getenv("LR2_FP8_256");
-      env256 = e2 ? atoi(e2) : 1;
-    }
-    const long t256 = (long)((M + 255) / 256) * ((N + 255) / 256), rounds = (t256 + 255) / 256;
-    const uint64_t lim = 0xFFFFFD00ull;
-    if (env256 && t256 >= 256 && t256 * 100 >= 80 * rounds * 256 && (uint64_t)M * K <= lim && (uint64_t)N * K <= lim)
-      return launch_gemm256_mx(p, (hipStream_t)stream);
-  }
+  // one-workgroup-per-CU rounds are well filled; the 128 x 128 kernel below otherwise.
+  const long t256 = (long)((M + 255) / 256) * ((N + 255) / 256), rounds = (t256 + 255) / 256;
+  const uint64_t lim = 0xFFFFFD00ull;
+  if (t256 >= 256 && t256 * 100 >= 80 * rounds * 256 && (uint64_t)M * K <= lim && (uint64_t)N * K <= lim)
+    return launch_gemm256_mx(p, (hipStream_t)stream);
   const int tiles = ((M + 127) / 128) * (N / 128);
-  const char* e = getenv("LR2_FP8_LDS");          // 0: fragments straight from global memory (the first version; A/B)
-  if (e && atoi(e) == 0) {
-    if (out_q || out_hi || !out) return LR2_ERR_ARG;          // the first version writes fp32 only
-    LR2_LAUNCH(gemm_mxfp8_kernel, dim3(tiles), dim3(256), 0, (hipStream_t)stream, p);
-    return lr2_launch_status(__func__);
-  }
   static bool attr = false;
   if (!attr) {
     if (lr2_allow_dynamic_lds(gemm_mxfp8_lds_kernel, 65536, "gemm_mxfp8")) return LR2_ERR_LAUNCH;

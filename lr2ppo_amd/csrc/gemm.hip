@@ -23,7 +23,7 @@
 //   planes: the producer already wrote the operand as two bf16 planes [hi | lo] (same bytes as fp32).  Tiles go
 //           HBM -> LDS by LDS-DMA (buffer_load ... lds, 16 B/lane, no VGPRs, no VALU).  Default: ONE LDS image per
 //           workgroup and two workgroups per CU (measured 285-339 TFLOP/s fp32-equivalent on the head's shapes vs
-//           239-275 with a double-buffered image and one workgroup per CU; LR2_GEMM_DMA_STAGES=2 selects the latter).  The measured profile of the all-fp32 form showed its phases (loads, split, LDS
+//           239-275 with a double-buffered image and one workgroup per CU).  The measured profile of the all-fp32 form showed its phases (loads, split, LDS
 //           write, fragment reads, MFMA) adding up serially with the matrix pipe ~30 % busy; with planes the split is
 //           paid once by the producer's epilogue instead of once per consuming tile (24-98x), and the loop is
 //           DMA + ds_read + MFMA only.
@@ -328,6 +328,7 @@ template <int BM, int BN, int BK, int WM, int WN, bool TA, bool TB, int PASSES, 
 // 8-wave workgroups are meant to run two per CU = 4 waves per SIMD: cap the register allocation at 128 for them
 __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 1) void gemm_kernel(GemmParams g) {
   static_assert(NW == 4 || (APL && BPL), "8-wave workgroups exist for planes x planes operands only");
+  static_assert(BK == 64 || (APL && BPL), "32-deep tiles exist for planes x planes operands only");
   static_assert((BM / WM) * (BN / WN) == NW, "wave grid");
   constexpr int MI = WM / 16, NI = WN / 16;
   constexpr int WAVES_N = BN / WN;
@@ -408,7 +409,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 1) void gemm_kernel(GemmPara
     const int cur = t & 1;
     char* a_cur = lds_a + ((APL && dbuf) ? cur : 0) * A_STAGE;
     char* b_cur = lds_b + ((BPL && dbuf) ? cur : 0) * B_STAGE;
-    if (more && !(g.ablate & 2)) {  // tile t+1: HBM -> LDS (planes) or HBM -> VGPR (fp32) while tile t is multiplied
+    if (more) {  // tile t+1: HBM -> LDS (planes) or HBM -> VGPR (fp32) while tile t is multiplied
       if (APL) { if (dbuf) da.issue(rsrc_a, rsrc_a_lo, lds_a + (cur ^ 1) * A_STAGE, wave); }
       else ra.load(rsrc_a);
       if (BPL) { if (dbuf) db.issue(rsrc_b, rsrc_b_lo, lds_b + (cur ^ 1) * B_STAGE, wave); }
@@ -420,7 +421,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 1) void gemm_kernel(GemmPara
       compute_tile<BM, BN, BK, MI, NI, TA, TB, PASSES>(a_cur, b_cur, wm0, wn0, lane, acc);
     if (!APL || !BPL || !dbuf) {
       __syncthreads();  // every wave is done reading the single-buffered image(s)
-      if (more && !(g.ablate & 4)) {
+      if (more) {
         if (!APL) ra.store(lds_a);
         else if (!dbuf) da.issue(rsrc_a, rsrc_a_lo, lds_a, wave);
         if (!BPL) rb.store(lds_b);
@@ -453,84 +454,77 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
   }
 }
 
-// Explicit instantiation of every kernel the dispatcher can reach: hipcc (ROCm 7.2) emits the host launch stub for only
-// a few of the implicit instantiations of this 9-parameter kernel template, leaving the others undefined at load time.
-#define LR2_GEMM_INST(BM, BK, WN, TA, TB, P, APL, BPL) \
-  template __global__ void gemm_kernel<BM, 128, BK, 64, WN, TA, TB, P, APL, BPL>(GemmParams);
-#define LR2_GEMM_INST_SRC(BM, WN, TA, TB, P)        \
-  LR2_GEMM_INST(BM, 64, WN, TA, TB, P, false, false) \
-  LR2_GEMM_INST(BM, 64, WN, TA, TB, P, true, false)  \
-  LR2_GEMM_INST(BM, 64, WN, TA, TB, P, true, true)   \
-  LR2_GEMM_INST(BM, 32, WN, TA, TB, P, true, true)
-#define LR2_GEMM_INST_FORM(BM, WN, P)           \
-  LR2_GEMM_INST_SRC(BM, WN, false, false, P)     \
-  LR2_GEMM_INST_SRC(BM, WN, false, true, P)      \
-  LR2_GEMM_INST_SRC(BM, WN, true, true, P)
-#define LR2_GEMM_INST_W8(BK, TA, TB) \
-  template __global__ void gemm_kernel<128, 128, BK, 64, 32, TA, TB, 3, true, true, 8>(GemmParams);
-LR2_GEMM_INST_W8(64, false, false)
-LR2_GEMM_INST_W8(32, false, false)
-LR2_GEMM_INST_W8(32, false, true)
-LR2_GEMM_INST_FORM(128, 64, 1)
-LR2_GEMM_INST_FORM(128, 64, 3)
-LR2_GEMM_INST_FORM(64, 32, 1)
-LR2_GEMM_INST_FORM(64, 32, 3)
+// K-tile depth of the general family.  Planes x planes with a contraction-strided B (NN, TN): 32-deep K tiles, two LDS stages
+// (64 KB), two workgroups per CU -- measured +10-14 % on the wgrad shapes; NT and anything with an fp32 operand: 64-deep tiles,
+// one stage (one image + 2 workgroups/CU measured faster than two images + 1 workgroup/CU).
+constexpr int gemm_bk(bool apl, bool bpl, bool tb) { return (apl && bpl && tb) ? 32 : 64; }
 
-template <int BM, int BN, int BK, int WM, int WN, bool TA, bool TB, int PASSES, bool APL, bool BPL>
+// Explicit instantiation of every kernel the dispatcher can reach: hipcc (ROCm 7.2) emits the host launch stub for only
+// a few of the implicit instantiations of this 11-parameter kernel template, leaving the others undefined at load time.
+// The list must match launch() below: BK = gemm_bk(...), and 128-row planes x planes NT / NN tiles at 3 passes run as 8 waves.
+#define LR2_GEMM_INST(BM, WN, TA, TB, P, APL, BPL, NW) \
+  template __global__ void gemm_kernel<BM, 128, gemm_bk(APL, BPL, TB), 64, WN, TA, TB, P, APL, BPL, NW>(GemmParams);
+#define LR2_GEMM_INST_4W(TA, TB, APL, BPL)       \
+  LR2_GEMM_INST(64, 32, TA, TB, 1, APL, BPL, 4)  \
+  LR2_GEMM_INST(64, 32, TA, TB, 3, APL, BPL, 4)  \
+  LR2_GEMM_INST(128, 64, TA, TB, 1, APL, BPL, 4)
+#define LR2_GEMM_INST_FORM(TA, TB, APL, BPL) \
+  LR2_GEMM_INST_4W(TA, TB, APL, BPL)         \
+  LR2_GEMM_INST(128, 64, TA, TB, 3, APL, BPL, 4)
+#define LR2_GEMM_INST_FORMS(APL, BPL)         \
+  LR2_GEMM_INST_FORM(false, false, APL, BPL)  \
+  LR2_GEMM_INST_FORM(false, true, APL, BPL)   \
+  LR2_GEMM_INST_FORM(true, true, APL, BPL)
+LR2_GEMM_INST_FORMS(false, false)
+LR2_GEMM_INST_FORMS(true, false)
+LR2_GEMM_INST_FORM(true, true, true, true)
+LR2_GEMM_INST_4W(false, false, true, true)
+LR2_GEMM_INST(128, 32, false, false, 3, true, true, 8)
+LR2_GEMM_INST_4W(false, true, true, true)
+LR2_GEMM_INST(128, 32, false, true, 3, true, true, 8)
+
+template <int BM, bool TA, bool TB, int PASSES, bool APL, bool BPL>
 int launch(const GemmParams& p_in, int splits, hipStream_t stream) {
+  constexpr int BN = 128, BK = gemm_bk(APL, BPL, TB);
+  // 128 x 128 planes tiles, NT / NN: 8-wave workgroups (two workgroups per CU = 4 waves per SIMD, wave tile 64 x 32) overlap the
+  // MFMA issue, the LDS-DMA issue and the fragment waits of different waves: +5..21 % over 4 waves (tools/gemm_bench.py); TN: equal.
+  constexpr int NW = (APL && BPL && BM == 128 && PASSES == 3 && !TA) ? 8 : 4;
+  constexpr int WM = 64, WN = (BM == 128 && NW == 4) ? 64 : 32;
   GemmParams p = p_in;
   p.tiles_m = (p.M + BM - 1) / BM;
   p.tiles_n = (p.N + BN - 1) / BN;
   p.splits = splits;
-  if (splits <= 1) p.partial = nullptr;     // (a diagnostics build may pass a workspace for other purposes)
+  p.dma_stages = BK == 32 ? 2 : 1;
   dim3 grid(p.tiles_m * p.tiles_n * splits);
-  constexpr int NIMG = PASSES == 3 ? 2 : 1;
-  const size_t main_lds = (size_t)((APL && p.dma_stages == 2) ? 2 : 1) * NIMG * BM * BK * 2 +
-                          (size_t)((BPL && p.dma_stages == 2) ? 2 : 1) * NIMG * BN * BK * 2;
-  constexpr size_t epi_lds = (size_t)4 * 32 * (WN + 4) * 4;
+  constexpr int nimg = PASSES == 3 ? 2 : 1;
+  const size_t main_lds = (size_t)p.dma_stages * nimg * (BM + BN) * BK * 2;
+  constexpr size_t epi_lds = (size_t)NW * 32 * (WN + 4) * 4;
   const size_t lds = main_lds > epi_lds ? main_lds : epi_lds;
-  constexpr size_t max_lds = (size_t)2 * NIMG * BM * BK * 2 + (size_t)2 * NIMG * BN * BK * 2;
-  // 8-wave workgroups: NT at either K depth, NN at 32-deep tiles (lr2_gemm never asks for them with a transposed A, and the
-  // 64-deep NN variant does not fit 128 VGPRs without scratch: it is not built)
-  if constexpr (APL && BPL && BM == 128 && PASSES == 3 && !TA && !(TB && BK == 64)) {
-    if (p.waves8) {   // 8 waves per workgroup, wave tile 64 x 32
-      auto k8 = gemm_kernel<128, 128, BK, 64, 32, TA, TB, 3, true, true, 8>;
-      constexpr size_t epi8 = (size_t)8 * 32 * (32 + 4) * 4;
-      const size_t lds8 = main_lds > epi8 ? main_lds : epi8;
-      static bool attr_set8 = false;
-      if (!attr_set8) {
-        if (lr2_allow_dynamic_lds(k8, max_lds > epi8 ? max_lds : epi8, "gemm")) return LR2_ERR_LAUNCH;
-        attr_set8 = true;
-      }
-      LR2_LAUNCH(k8, grid, dim3(512), lds8, stream, p);
-      return lr2_launch_status(__func__);
-    }
-  }
-  auto kern = gemm_kernel<BM, BN, BK, WM, WN, TA, TB, PASSES, APL, BPL>;
+  auto kern = gemm_kernel<BM, BN, BK, WM, WN, TA, TB, PASSES, APL, BPL, NW>;
   static bool attr_set = false;
   if (!attr_set) {
-    if (lr2_allow_dynamic_lds(kern, max_lds > epi_lds ? max_lds : epi_lds, "gemm")) return LR2_ERR_LAUNCH;
+    if (lr2_allow_dynamic_lds(kern, lds, "gemm")) return LR2_ERR_LAUNCH;
     attr_set = true;
   }
-  LR2_LAUNCH(kern, grid, dim3(NTHREADS), lds, stream, p);
+  LR2_LAUNCH(kern, grid, dim3(64 * NW), lds, stream, p);
   return lr2_launch_status(__func__);
 }
 
-template <int BK, bool TA, bool TB, bool APL, bool BPL>
+template <bool TA, bool TB, bool APL, bool BPL>
 int dispatch(const GemmParams& p, int splits, int bm, int passes, hipStream_t stream) {
   if (passes == 1) {
-    if (bm == 64) return launch<64, 128, BK, 64, 32, TA, TB, 1, APL, BPL>(p, splits, stream);
-    return launch<128, 128, BK, 64, 64, TA, TB, 1, APL, BPL>(p, splits, stream);
+    if (bm == 64) return launch<64, TA, TB, 1, APL, BPL>(p, splits, stream);
+    return launch<128, TA, TB, 1, APL, BPL>(p, splits, stream);
   }
-  if (bm == 64) return launch<64, 128, BK, 64, 32, TA, TB, 3, APL, BPL>(p, splits, stream);
-  return launch<128, 128, BK, 64, 64, TA, TB, 3, APL, BPL>(p, splits, stream);
+  if (bm == 64) return launch<64, TA, TB, 3, APL, BPL>(p, splits, stream);
+  return launch<128, TA, TB, 3, APL, BPL>(p, splits, stream);
 }
 
-template <int BK, bool APL, bool BPL>
+template <bool APL, bool BPL>
 int dispatch_form(const GemmParams& p, int splits, int bm, int passes, int ta, int tb, hipStream_t s) {
-  if (!ta && !tb) return dispatch<BK, false, false, APL, BPL>(p, splits, bm, passes, s);
-  if (!ta && tb) return dispatch<BK, false, true, APL, BPL>(p, splits, bm, passes, s);
-  if (ta && tb) return dispatch<BK, true, true, APL, BPL>(p, splits, bm, passes, s);
+  if (!ta && !tb) return dispatch<false, false, APL, BPL>(p, splits, bm, passes, s);
+  if (!ta && tb) return dispatch<false, true, APL, BPL>(p, splits, bm, passes, s);
+  if (ta && tb) return dispatch<true, true, APL, BPL>(p, splits, bm, passes, s);
   return LR2_ERR_ARG;  // (1,0) is not a form the path needs
 }
 
@@ -601,16 +595,11 @@ extern "C" int lr2_gemm_row_split_plan(int M, int N, int K, int* rows_256, int* 
   if (!rows_256 || !tail_block_m || M <= 0 || N <= 0 || K <= 0) return LR2_ERR_ARG;
   *rows_256 = 0;
   *tail_block_m = 128;
-  static int rs_env = -1;
-  if (rs_env < 0) {
-    const char* e = getenv("LR2_GEMM_ROWSPLIT");
-    rs_env = e ? atoi(e) : 1;
-  }
   const int tn256 = (N + 255) / 256, tiles256 = ((M + 255) / 256) * tn256;
   const int full = tiles256 / 256, rem = tiles256 - full * 256;
   const int M1 = ((full * 256) / tn256) * 256;          // rows of the tile rows that fit `full` rounds
   // (up to 4 whole rounds: behind 18 rounds -- the encoders at 512 frames -- a thin last round is 2 % of the launch, not worth a seam)
-  if (!rs_env || full < 1 || full > 4 || rem <= 0 || 2 * rem >= 256 || (K % 64) != 0 || M1 <= 0 || M1 >= M) return 0;
+  if (full < 1 || full > 4 || rem <= 0 || 2 * rem >= 256 || (K % 64) != 0 || M1 <= 0 || M1 >= M) return 0;
   *rows_256 = M1;
   // tail tiles: 64 rows when 128-row tiles would not fill the 512 resident slots, or would leave a thin last round
   const int M2 = M - M1, t128 = ((M2 + 127) / 128) * ((N + 127) / 128), last = t128 % 512;
@@ -630,37 +619,19 @@ extern "C" int lr2_gemm(const void* A, const void* B, int M, int N, int K, int l
   if (epi->colsum && (!trans_a || !trans_b || !epi->colsum_ws || (M % 4))) return LR2_ERR_ARG;   // weight-gradient form only
   const bool want256 = block_m == 256;
   if (block_m != 64) block_m = 128;
-  // K-contiguous operands need whole K tiles (a ragged K would read into the next row, not zeros); ragged M / N are
-  // handled by the zero-filling range check on loads plus masked stores.
-  static int bk_env = -1, ablate = -1, stages = -1, w8_env = 0;
-  if (ablate < 0) {
-    const char* e = getenv("LR2_GEMM_ABLATE");
-    ablate = e ? atoi(e) : 0;
-    const char* st = getenv("LR2_GEMM_DMA_STAGES");
-    stages = st ? atoi(st) : 0;
-    const char* bk = getenv("LR2_GEMM_BK");
-    bk_env = bk ? (atoi(bk) == 64 ? 64 : 32) : 0;
-    const char* w8 = getenv("LR2_GEMM_W8");
-    w8_env = w8 ? atoi(w8) : 1;
-  }
-  // planes x planes with a contraction-strided B (NN, TN): 32-deep K tiles, two LDS stages (64 KB), two workgroups per
-  // CU -- measured +10-14 % on the wgrad shapes; NT and anything with an fp32 operand: 64-deep tiles, one stage.
-  static int g256_env = -1;
-  if (g256_env < 0) {
-    const char* e = getenv("LR2_GEMM_256");
-    g256_env = e ? atoi(e) : 1;
-  }
   // Large NT products of planes: the 256 x 256 ping-pong kernel (gemm256.hip, 32-deep K steps) when the caller asks for it
   // (block_m == 256) and the shape is eligible; otherwise the general kernel family.
-  const bool use256 = want256 && g256_env && a_planes && b_planes && !trans_a && !trans_b && passes == 3 && splits <= 1 &&
+  const bool use256 = want256 && a_planes && b_planes && !trans_a && !trans_b && passes == 3 && splits <= 1 &&
                       (K % 32) == 0 && a_bytes <= 0xFFFFFD00ull && b_bytes <= 0xFFFFFD00ull && !epi->adam_p &&
                       ((epi->act == 2) + (epi->resid != nullptr) + (epi->accumulate != 0)) <= 1;   // one request slot per element
   // Long-contraction TN products of planes (weight gradients at >= 4096 token rows): the TN form of that kernel, tiles x K-splits
   // in one round of the chip, raw slabs + the reducer below.
-  const bool use256tn = want256 && g256_env && a_planes && b_planes && trans_a && trans_b && passes == 3 &&
+  const bool use256tn = want256 && a_planes && b_planes && trans_a && trans_b && passes == 3 &&
                         a_bytes <= 0xFFFFFD00ull && b_bytes <= 0xFFFFFD00ull && !epi->adam_p &&
                         ((epi->act == 2) + (epi->resid != nullptr) + (epi->accumulate != 0)) <= 1;
-  const int BK = (use256 || use256tn) ? 32 : (a_planes && b_planes) ? (bk_env ? bk_env : (trans_b ? 32 : 64)) : 64;
+  const int BK = (use256 || use256tn) ? 32 : gemm_bk(a_planes, b_planes, trans_b);
+  // K-contiguous operands need whole K tiles (a ragged K would read into the next row, not zeros); ragged M / N are
+  // handled by the zero-filling range check on loads plus masked stores.
   if ((!trans_a || !trans_b) && (K % BK != 0)) return LR2_ERR_SHAPE;
   const int a_align = a_planes ? 8 : 4, b_align = b_planes ? 8 : 4;  // 16-byte rows
   if ((lda % a_align) || (ldb % b_align) || (N % 4)) return LR2_ERR_SHAPE;
@@ -689,19 +660,15 @@ extern "C" int lr2_gemm(const void* A, const void* B, int M, int N, int K, int l
   p.b_lo_off = (uint32_t)b_lo_off;
   p.k_tiles_per_split = (total_k_tiles + splits - 1) / splits;
   splits = (total_k_tiles + p.k_tiles_per_split - 1) / p.k_tiles_per_split;
-  p.partial = (splits > 1 || (ablate & 32)) ? (float*)splitk_ws : nullptr;
+  p.partial = splits > 1 ? (float*)splitk_ws : nullptr;
+  static const bool epi_general = getenv("LR2_GEMM_EPI_GENERAL") && atoi(getenv("LR2_GEMM_EPI_GENERAL")) == 1;
+  p.epi_general = epi_general;
   p.epi = to_device_epilogue(epi);
-  p.epi.stream_nt = (ablate & 64) ? 0 : 1;   // fused AdamW: +2-3 % on the 12-GB p / m / v stream (A/B with LR2_GEMM_ABLATE=64)
-  p.ablate = ablate;
+  p.epi.stream_nt = 1;   // fused AdamW: +2-3 % on the 12-GB p / m / v stream
   // Results of 256 MiB and more (the encoders' token GEMMs at M >= 1e5 rows: larger than L2 + the 256-MiB MALL, streamed from HBM by
-  // the next kernel whatever we do) are stored non-temporally: +1..4 % on the K = 768 shapes of the 256 x 256 kernel, A/B with
-  // LR2_GEMM_ABLATE=128 (= off).  Smaller results keep the default policy: their consumer may still find them on chip.
-  p.epi.store_nt = (!(ablate & 128) && (uint64_t)M * (uint64_t)N * 4ull >= (256ull << 20)) ? 1 : 0;
-  // 128 x 128 planes tiles, NT / NN: 8-wave workgroups (two workgroups per CU = 4 waves per SIMD) overlap the MFMA issue,
-  // the LDS-DMA issue and the fragment waits of different waves: +5..21 % over 4 waves (tools/gemm_bench.py); TN: equal.
-  p.waves8 = (w8_env && !trans_a) ? 1 : 0;
-  // 64-deep planes tiles: one image + 2 workgroups/CU measured faster than two images + 1 workgroup/CU
-  p.dma_stages = stages ? (stages == 1 ? 1 : 2) : (BK == 32 ? 2 : 1);
+  // the next kernel whatever we do) are stored non-temporally: +1..4 % on the K = 768 shapes of the 256 x 256 kernel.  Smaller
+  // results keep the default policy: their consumer may still find them on chip.
+  p.epi.store_nt = (uint64_t)M * (uint64_t)N * 4ull >= (256ull << 20) ? 1 : 0;
   hipStream_t s = (hipStream_t)stream;
   int rc;
   if (use256) {
@@ -735,8 +702,7 @@ extern "C" int lr2_gemm(const void* A, const void* B, int M, int N, int K, int l
       if (e2.out_hi) e2.out_hi += (size_t)M1 * e2.ld_planes;
       p2.k_tiles_per_split = K / 64;
       p2.partial = nullptr;
-      p2.dma_stages = stages ? (stages == 1 ? 1 : 2) : 1;
-      return dispatch_form<64, true, true>(p2, 1, bm2, 3, 0, 0, s);
+      return dispatch_form<true, true>(p2, 1, bm2, 3, 0, 0, s);
     }
     ++g_launches[0];
     return launch_gemm256_nt(p, s);
@@ -745,10 +711,9 @@ extern "C" int lr2_gemm(const void* A, const void* B, int M, int N, int K, int l
   if (fused_colsum) p.epi.colsum_partial = (float*)epi->colsum_ws;
   ++g_launches[use256tn ? 1 : 2];
   if (use256tn) rc = launch_gemm256_tn(p, splits, s);
-  else if (a_planes && b_planes && BK == 32) rc = dispatch_form<32, true, true>(p, splits, block_m, passes, trans_a, trans_b, s);
-  else if (a_planes && b_planes) rc = dispatch_form<64, true, true>(p, splits, block_m, passes, trans_a, trans_b, s);
-  else if (a_planes) rc = dispatch_form<64, true, false>(p, splits, block_m, passes, trans_a, trans_b, s);
-  else rc = dispatch_form<64, false, false>(p, splits, block_m, passes, trans_a, trans_b, s);
+  else if (a_planes && b_planes) rc = dispatch_form<true, true>(p, splits, block_m, passes, trans_a, trans_b, s);
+  else if (a_planes) rc = dispatch_form<true, false>(p, splits, block_m, passes, trans_a, trans_b, s);
+  else rc = dispatch_form<false, false>(p, splits, block_m, passes, trans_a, trans_b, s);
   if (rc) return rc;
   if (splits > 1) {
     const size_t total4 = (size_t)M * N / 4;

@@ -24,8 +24,6 @@
 //     bank row: conflict-free ds_read_b128); LDS-DMA writes lane-linearly, so the swizzle is applied to the SOURCE address.
 //   * hazards: a fragment read happens at least one barrier after every wave's counted wait for that part (RAW); a part is
 //     refilled one barrier after both groups' reads of it were retired by lgkmcnt(0) (WAR).
-#include <stdlib.h>
-
 #include "gemm_common.h"
 
 namespace lr2gemm {
@@ -126,34 +124,29 @@ __device__ __forceinline__ void mfma_section(f32x4_t (&acc)[2 * MIH][4], const b
 }
 
 // One K step (tile t, compile-time stage S).  A part may be refilled once its last reader has passed (A0 after load
-// section 0, B1 after 1, A1 after 2, B0 after 3).  Two placements of the refills (V, A/B-tested in one process with
-// LR2_GEMM256_VARIANT):
-//   V = 0: as early as possible, 2 pieces per section: 0: B0(t+1) [other stage]  1: A0(t+2)  2: B1(t+2)  3: A1(t+2)
-//   V = 1: in the two light sections only (no section carries 12 fragment reads AND DMA issue):
-//          1: B0(t+1), A0(t+2)   3: B1(t+2), A1(t+2)
+// section 0, B1 after 1, A1 after 2, B0 after 3); the refills go as early as possible, 2 pieces per section:
+//   0: B0(t+1) [other stage]  1: A0(t+2)  2: B1(t+2)  3: A1(t+2)
 // The counted waits leave exactly the parts issued after the one the NEXT section reads in flight (2 pieces per part).
-template <int S, int V, int MIH>
+template <int S, int MIH>
 __device__ __forceinline__ void k_step(const Ctx& c, int t, f32x4_t (&acc)[2 * MIH][4]) {
   bf16x8_t ahi[MIH], alo[MIH], bhi[2], blo[2];
   // phase 0: quadrant (A0, B0)
-  if (V == 0) issue_part<SLOT_B0, false, 0>(c, t + 1, S ^ 1);
+  issue_part<SLOT_B0, false, 0>(c, t + 1, S ^ 1);
   read_a_half<SLOT_A0, MIH>(c.rd_a[S], ahi, alo);
   read_b_half<SLOT_B0>(c.rd_b[S], bhi, blo);
-  end_load_section<V == 0 ? 12 : 10>();
+  end_load_section<12>();
   mfma_section<0, 0, MIH>(acc, ahi, alo, bhi, blo);
   // phase 1: (A0, B1)
-  if (V == 1) issue_part<SLOT_B0, false, 0>(c, t + 1, S ^ 1);
   issue_part<SLOT_A0, true, 0>(c, t + 2, S);
   read_b_half<SLOT_B1>(c.rd_b[S], bhi, blo);
   end_load_section<12>();
   mfma_section<0, 1, MIH>(acc, ahi, alo, bhi, blo);
   // phase 2: (A1, B1)
-  if (V == 0) issue_part<SLOT_B1, false, 1>(c, t + 2, S);
+  issue_part<SLOT_B1, false, 1>(c, t + 2, S);
   read_a_half<SLOT_A1, MIH>(c.rd_a[S], ahi, alo);
-  end_load_section<V == 0 ? 12 : 10>();
+  end_load_section<12>();
   mfma_section<1, 1, MIH>(acc, ahi, alo, bhi, blo);
   // phase 3: (A1, B0)
-  if (V == 1) issue_part<SLOT_B1, false, 1>(c, t + 2, S);
   issue_part<SLOT_A1, true, 1>(c, t + 2, S);
   read_b_half<SLOT_B0>(c.rd_b[S], bhi, blo);
   end_load_section<6>();
@@ -164,7 +157,7 @@ __device__ __forceinline__ void k_step(const Ctx& c, int t, f32x4_t (&acc)[2 * M
 // of less than one round of 256-row tiles that fit one round of 192-row tiles too (M = 12 544, N = 768: 147 -> 198 workgroups, each
 // with three quarters of the work).  Same ring: an A part then holds 96 rows, the two waves whose 16-row pieces fall beyond them issue
 // out-of-range requests (zeros into the unused quarter of the part), so every wave's counted waits stay as they are.
-template <int V, int MIH = 4>
+template <int MIH>
 __global__ __launch_bounds__(512, 2) void gemm256_nt_kernel(GemmParams g) {
   constexpr int BMT = 64 * MIH, WMT = 32 * MIH;      // tile rows, wave-tile rows
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -174,13 +167,13 @@ __global__ __launch_bounds__(512, 2) void gemm256_nt_kernel(GemmParams g) {
   const int wr = wave >> 2, wc = wave & 3;
 
   int tm, tn;
-  tile_coords(g.tiles_m, g.tiles_n, blockIdx.x, tm, tn, g.strip_n > 0 ? g.strip_n : 8);
+  tile_coords(g.tiles_m, g.tiles_n, blockIdx.x, tm, tn);
   const int m0 = tm * BMT, n0 = tn * BN;
 
   Ctx c;
   c.smem = smem;
   c.wave = wave;
-  c.nt = (g.ablate & 16) ? 0 : g.K / BK;      // diagnostics (LR2_GEMM_ABLATE): 16 = no main loop, 8 = no epilogue memory traffic
+  c.nt = g.K / BK;
   c.a_hi = uniform_rsrc(g.A, g.a_bytes);
   c.a_lo = uniform_rsrc((const char*)g.A + g.a_lo_off, g.a_bytes);
   c.b_hi = uniform_rsrc(g.B, g.b_bytes);
@@ -230,22 +223,9 @@ __global__ __launch_bounds__(512, 2) void gemm256_nt_kernel(GemmParams g) {
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
   }
-  // diagnostics (LR2_GEMM_ABLATE & 32, never in a timed run): shader cycles and 100 MHz ticks of the main loop, per
-  // workgroup, into the split-K workspace pointer (unused by this kernel) -> the clock the chip holds under this load
-  uint64_t tc0 = 0, tr0 = 0;
-  if (g.ablate & 32) {
-    tc0 = __builtin_amdgcn_s_memtime();
-    tr0 = __builtin_amdgcn_s_memrealtime();
-  }
   for (int t = 0; t < c.nt; t += 2) {
-    k_step<0, V, MIH>(c, t, acc);
-    if (t + 1 < c.nt) k_step<1, V, MIH>(c, t + 1, acc);
-  }
-  if ((g.ablate & 32) && g.partial && tid == 0) {
-    const uint64_t tc1 = __builtin_amdgcn_s_memtime(), tr1 = __builtin_amdgcn_s_memrealtime();
-    uint64_t* dbg = reinterpret_cast<uint64_t*>(g.partial) + 2 * (size_t)blockIdx.x;
-    dbg[0] = tc1 - tc0;
-    dbg[1] = tr1 - tr0;
+    k_step<0, MIH>(c, t, acc);
+    if (t + 1 < c.nt) k_step<1, MIH>(c, t + 1, acc);
   }
   if (wr == 0) {                                // same number of barriers for every wave
     __builtin_amdgcn_s_barrier();
@@ -256,12 +236,6 @@ __global__ __launch_bounds__(512, 2) void gemm256_nt_kernel(GemmParams g) {
   __builtin_amdgcn_sched_barrier(0);
 
   float* slab = reinterpret_cast<float*>(smem) + wave * (32 * (64 + 4));
-  if (g.ablate & 8) {
-    GemmParams g2 = g;
-    g2.M = 0;
-    epilogue_wave<WMT, 64, 2 * MIH, 4, 1>(g2, acc, slab, m0 + wr * WMT, n0 + wc * 64, lane, nullptr);
-    return;
-  }
   epilogue_wave<WMT, 64, 2 * MIH, 4, 1>(g, acc, slab, m0 + wr * WMT, n0 + wc * 64, lane, nullptr);
 }
 
@@ -367,7 +341,7 @@ __device__ __forceinline__ void colsum_frags(float (&cs)[2], int wc, const bf16x
   else cs[AH] += frag_sum(ahi[3]) + frag_sum(alo[3]);
 }
 
-// One K step; the section / refill / counted-wait schedule of g256::k_step<S, 0>.  do_cs (wave-uniform): this wave adds the K
+// One K step; the section / refill / counted-wait schedule of g256::k_step.  do_cs (wave-uniform): this wave adds the K
 // step's A fragments to its column sums (after the MFMAs of the phase were issued: the vector work runs under the matrix pipe).
 template <int S>
 __device__ __forceinline__ void k_step(const Ctx& c, int t, f32x4_t (&acc)[8][4], float (&cs)[2], int wc, bool do_cs) {
@@ -516,7 +490,6 @@ int launch_gemm256_tn(const GemmParams& p_in, int splits, hipStream_t stream) {
   p.tiles_m = (p.M + BM - 1) / BM;
   p.tiles_n = (p.N + BN - 1) / BN;
   p.splits = splits;
-  if (splits <= 1) p.partial = nullptr;
   static bool attr_set = false;
   if (!attr_set) {
     if (lr2_allow_dynamic_lds(gemm256_tn_kernel, LDS_BYTES, "gemm256_tn")) return LR2_ERR_LAUNCH;
@@ -529,12 +502,11 @@ int launch_gemm256_tn(const GemmParams& p_in, int splits, hipStream_t stream) {
 // Host entry for gemm.hip's dispatcher.  Requirements (checked by the caller): planes x planes, NT, passes == 3,
 // K % 32 == 0, no split-K, operand extents < 4 GiB - 512 B.
 // rows per tile the NT launcher picks for a shape: 192 when one round of 256-row tiles would leave CUs idle that a round of 192-row
-// tiles fills (LR2_GEMM_192=0: always 256; read once per process)
+// tiles fills
 int gemm256_nt_tile_rows(int M, int N) {
-  static const bool on = !(getenv("LR2_GEMM_192") && atoi(getenv("LR2_GEMM_192")) == 0);
   const int tn = (N + g256::BN - 1) / g256::BN;
   const int t256 = ((M + 255) / 256) * tn, t192 = ((M + 191) / 192) * tn;
-  return (on && t256 < 256 && t192 <= 256 && t192 > t256) ? 192 : 256;
+  return (t256 < 256 && t192 <= 256 && t192 > t256) ? 192 : 256;
 }
 
 int launch_gemm256_nt(const GemmParams& p_in, hipStream_t stream) {
@@ -543,21 +515,14 @@ int launch_gemm256_nt(const GemmParams& p_in, hipStream_t stream) {
   const int bm = gemm256_nt_tile_rows(p.M, p.N);
   p.tiles_m = (p.M + bm - 1) / bm;
   p.tiles_n = (p.N + BN - 1) / BN;
-  if (!(p.ablate & 32)) p.partial = nullptr;
   static bool attr_set = false;
   if (!attr_set) {
-    if (lr2_allow_dynamic_lds(gemm256_nt_kernel<0, 4>, LDS_BYTES, "gemm256")) return LR2_ERR_LAUNCH;
-    if (lr2_allow_dynamic_lds(gemm256_nt_kernel<1, 4>, LDS_BYTES, "gemm256")) return LR2_ERR_LAUNCH;
-    if (lr2_allow_dynamic_lds(gemm256_nt_kernel<0, 3>, LDS_BYTES, "gemm256(192 rows)")) return LR2_ERR_LAUNCH;
+    if (lr2_allow_dynamic_lds(gemm256_nt_kernel<4>, LDS_BYTES, "gemm256")) return LR2_ERR_LAUNCH;
+    if (lr2_allow_dynamic_lds(gemm256_nt_kernel<3>, LDS_BYTES, "gemm256(192 rows)")) return LR2_ERR_LAUNCH;
     attr_set = true;
   }
-  const char* se = getenv("LR2_GEMM_STRIP");          // read per call: strip width of the tile order (A/B inside one process)
-  p.strip_n = se ? atoi(se) : 0;
-  const char* ve = getenv("LR2_GEMM256_VARIANT");     // read per call: tools A/B the variants inside one process
-  const int variant = ve ? atoi(ve) : 0;
-  if (bm == 192) LR2_LAUNCH((gemm256_nt_kernel<0, 3>), dim3(p.tiles_m * p.tiles_n), dim3(512), LDS_BYTES, stream, p);
-  else if (variant == 1) LR2_LAUNCH((gemm256_nt_kernel<1, 4>), dim3(p.tiles_m * p.tiles_n), dim3(512), LDS_BYTES, stream, p);
-  else LR2_LAUNCH((gemm256_nt_kernel<0, 4>), dim3(p.tiles_m * p.tiles_n), dim3(512), LDS_BYTES, stream, p);
+  if (bm == 192) LR2_LAUNCH(gemm256_nt_kernel<3>, dim3(p.tiles_m * p.tiles_n), dim3(512), LDS_BYTES, stream, p);
+  else LR2_LAUNCH(gemm256_nt_kernel<4>, dim3(p.tiles_m * p.tiles_n), dim3(512), LDS_BYTES, stream, p);
   return lr2_launch_status(__func__);
 }
 

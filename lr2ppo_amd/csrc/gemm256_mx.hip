@@ -23,7 +23,6 @@
 //     (2 DMA instructions per part, 1 per scale step; each count = the DMAs issued after the youngest part the NEXT section reads).
 //   * epilogue through a wave-private LDS slab, 32 rows at a time: bias, GELU, residual; results as fp32, as bf16 hi / lo planes
 //     (what the attention kernels read) and / or re-quantised to MX-FP8 (the next product's A operand).
-#include <stdlib.h>
 
 #include "fp8_common.h"
 #include "gemm_common.h"
@@ -112,7 +111,7 @@ __device__ __forceinline__ void read_b_half(uint32_t base, v8i_t (&b)[2]) {
 }
 // scales of accumulator half AH / BH for stage S: A rows wr*128 + AH*64 + 16 i + r16, B rows wc*64 + BH*32 + 16 j + r16
 // SC16 form: the scale bytes of FOUR K steps per row and DMA (16 B per lane): a 4-byte gather per lane and step touched one cache
-// line per row and step -- as many L2 -> L1 bytes as the operands themselves, 0.56 of 2.21 us per K step (tools/dbg/mx_ablate.py)
+// line per row and step -- as many L2 -> L1 bytes as the operands themselves, 0.56 of 2.21 us per K step (profiles/experiments/README.md F.3)
 __device__ __forceinline__ void issue_scales16(const Ctx& c, int quad, int stage) {
   const uint32_t off = (uint32_t)quad * 16u;
   const uint32_t v = (off < (uint32_t)c.ks && c.voff_s != OOB) ? c.voff_s + off : OOB;
@@ -154,79 +153,70 @@ __device__ __forceinline__ void end_load_section() {
 }
 
 // 8 instructions of one accumulator quadrant (K = 128 each)
-template <int AH, int BH, int ABL = 0>
+template <int AH, int BH>
 __device__ __forceinline__ void mfma_section(f32x4_t (&acc)[8][4], const v8i_t (&a)[4], const v8i_t (&b)[2], const int (&sa)[4],
                                              const int (&sb)[2]) {
   __builtin_amdgcn_s_setprio(1);
-  if constexpr (ABL & 4) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) asm volatile("" ::"v"(a[i]), "v"(sa[i]));
-    asm volatile("" ::"v"(b[0]), "v"(b[1]), "v"(sb[0]), "v"(sb[1]));
-  } else {
 #pragma unroll
   for (int j = 0; j < 2; ++j)
 #pragma unroll
     for (int i = 0; i < 4; ++i)
       acc[AH * 4 + i][BH * 2 + j] =
           __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a[i], b[j], acc[AH * 4 + i][BH * 2 + j], 0, 0, 0, sa[i], 0, sb[j]);
-  }
   __builtin_amdgcn_s_setprio(0);
   __builtin_amdgcn_sched_barrier(0);
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_sched_barrier(0);
 }
 
-// ABL (diagnostics, LR2_MX_ABLATE, never in a timed product run): 1 = no scale traffic (unit scales), 2 = no operand DMA,
-// 4 = no matrix instructions, 8 = no epilogue
-template <int S, int ABL, bool SC16>
+template <int S, bool SC16>
 __device__ __forceinline__ void k_step(const Ctx& c, int t, f32x4_t (&acc)[8][4]) {
   v8i_t a[4], b[2];
-  int sa[4] = {127, 127, 127, 127}, sb0[2] = {127, 127}, sb1[2] = {127, 127};
-  constexpr bool SC = !(ABL & 1);
+  int sa[4], sb0[2], sb1[2];
   // SC16: the step's scales sit in stage (t >> 2) & 1 at byte 4 (t & 3) of the lane's row
   const uint32_t soff = SC16 ? (uint32_t)(((t >> 2) & 1) * SC16_STAGE + (t & 3) * 4) : 0u;
   const uint32_t rsa = c.rd_sa + soff, rsb = c.rd_sb + soff;
   // the waits: SC16 issues a scale DMA in one step of four only, so the counts are those of the operand parts alone (an extra DMA in
   // flight makes a counted wait stricter, never laxer); the 4-byte form issues one per step and counts it
-  constexpr int W0 = (ABL & 2) ? 0 : (SC && !SC16) ? 14 : 12, W2 = (ABL & 2) ? 0 : (SC && !SC16) ? 13 : 12, W3 = (ABL & 2) ? 0 : (SC && !SC16) ? 7 : 6;
+  constexpr int W0 = SC16 ? 12 : 14, W2 = SC16 ? 12 : 13, W3 = SC16 ? 6 : 7;
   // phase 0: quadrant (A0, B0)
-  if (!(ABL & 2)) issue_part<SLOT_B0, false, 0>(c, t + 1, S ^ 1);
+  issue_part<SLOT_B0, false, 0>(c, t + 1, S ^ 1);
   read_a_half<SLOT_A0>(c.rd_a[S], a);
   read_b_half<SLOT_B0>(c.rd_b[S], b);
-  if constexpr (SC && SC16) {
+  if constexpr (SC16) {
     read_sa16<0>(rsa, sa);
     read_sb16<0>(rsb, sb0);
-  } else if constexpr (SC) {
+  } else {
     read_sa<S, 0>(c.rd_sa, sa);
     read_sb<S, 0>(c.rd_sb, sb0);
   }
   end_load_section<W0>();
-  mfma_section<0, 0, ABL>(acc, a, b, sa, sb0);
+  mfma_section<0, 0>(acc, a, b, sa, sb0);
   // phase 1: (A0, B1)
-  if (!(ABL & 2)) issue_part<SLOT_A0, true, 0>(c, t + 2, S);
+  issue_part<SLOT_A0, true, 0>(c, t + 2, S);
   read_b_half<SLOT_B1>(c.rd_b[S], b);
-  if constexpr (SC && SC16) read_sb16<1>(rsb, sb1);
-  else if constexpr (SC) read_sb<S, 1>(c.rd_sb, sb1);
+  if constexpr (SC16) read_sb16<1>(rsb, sb1);
+  else read_sb<S, 1>(c.rd_sb, sb1);
   end_load_section<W0>();
-  mfma_section<0, 1, ABL>(acc, a, b, sa, sb1);
+  mfma_section<0, 1>(acc, a, b, sa, sb1);
   // phase 2: (A1, B1)
-  if (!(ABL & 2)) issue_part<SLOT_B1, false, 1>(c, t + 2, S);
+  issue_part<SLOT_B1, false, 1>(c, t + 2, S);
   read_a_half<SLOT_A1>(c.rd_a[S], a);
-  if constexpr (SC && SC16) read_sa16<1>(rsa, sa);
-  else if constexpr (SC) read_sa<S, 1>(c.rd_sa, sa);
+  if constexpr (SC16) read_sa16<1>(rsa, sa);
+  else read_sa<S, 1>(c.rd_sa, sa);
   end_load_section<W2>();
-  mfma_section<1, 1, ABL>(acc, a, b, sa, sb1);
+  mfma_section<1, 1>(acc, a, b, sa, sb1);
   // phase 3: (A1, B0); every scale read of step t was retired one barrier ago by both groups.  4-byte form: the step's slot takes
   // step t + 2.  SC16: at the first step of a quad the OTHER stage (last read in step t - 1) takes the next quad.
-  if (!(ABL & 2)) issue_part<SLOT_A1, true, 1>(c, t + 2, S);
-  if constexpr (SC && SC16) {
+  issue_part<SLOT_A1, true, 1>(c, t + 2, S);
+  if constexpr (SC16) {
     if ((t & 3) == 0) issue_scales16(c, (t >> 2) + 1, ((t >> 2) + 1) & 1);
-  } else if constexpr (SC) {
+  } else {
     issue_scales(c, t + 2, S);
   }
   read_b_half<SLOT_B0>(c.rd_b[S], b);
   end_load_section<W3>();
-  mfma_section<1, 0, ABL>(acc, a, b, sa, sb0);
+  mfma_section<1, 0>(acc, a, b, sa, sb0);
 }
 
 // ---- epilogue: one 32-row slab of the wave tile (accumulator tile rows 2 HALF, 2 HALF + 1) --------------------------------------
@@ -347,7 +337,7 @@ __device__ __forceinline__ void epilogue_slab(const Mx8Params& p, f32x4_t (&acc)
   }
 }
 
-template <int ABL, bool SC16>
+template <bool SC16>
 __global__ __launch_bounds__(512, 2) void gemm256_mx_kernel(Mx8Params p, int tiles_m, int tiles_n) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
@@ -423,8 +413,8 @@ __global__ __launch_bounds__(512, 2) void gemm256_mx_kernel(Mx8Params p, int til
     __builtin_amdgcn_sched_barrier(0);
   }
   for (int t = 0; t < c.nt; t += 2) {
-    k_step<0, ABL, SC16>(c, t, acc);
-    if (t + 1 < c.nt) k_step<1, ABL, SC16>(c, t + 1, acc);
+    k_step<0, SC16>(c, t, acc);
+    if (t + 1 < c.nt) k_step<1, SC16>(c, t + 1, acc);
   }
   if (wr == 0) {                                // same number of barriers for every wave
     __builtin_amdgcn_s_barrier();
@@ -435,13 +425,6 @@ __global__ __launch_bounds__(512, 2) void gemm256_mx_kernel(Mx8Params p, int til
   __builtin_amdgcn_sched_barrier(0);
 
   const int mw = m0 + wr * 128, nw = n0 + wc * 64;
-  if constexpr (ABL == 8) {                     // diagnostics: no epilogue at all (the accumulators are kept alive)
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) asm volatile("" ::"v"(acc[i][j]));
-    return;
-  }
   if (nw + 64 > p.N || mw >= p.M) return;       // N % 128 == 0 <=> a wave's 64 columns are all inside or all outside
   float* slab = reinterpret_cast<float*>(smem) + wave * (32 * (64 + 4));
   float4 b4 = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -459,29 +442,16 @@ int launch_gemm256_mx(const Mx8Params& p, hipStream_t stream) {
   using namespace lr2mx256;
   const int tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.N + BN - 1) / BN;
   static bool attr_set = false;
-  static int abl = 0, sc16_env = 1;
   if (!attr_set) {
-    if (lr2_allow_dynamic_lds(gemm256_mx_kernel<0, false>, LDS_BYTES, "gemm256_mx")) return LR2_ERR_LAUNCH;
-    if (lr2_allow_dynamic_lds(gemm256_mx_kernel<0, true>, LDS_BYTES16, "gemm256_mx")) return LR2_ERR_LAUNCH;
-    if (lr2_allow_dynamic_lds(gemm256_mx_kernel<1, false>, LDS_BYTES, "gemm256_mx")) return LR2_ERR_LAUNCH;
-    if (lr2_allow_dynamic_lds(gemm256_mx_kernel<2, false>, LDS_BYTES, "gemm256_mx")) return LR2_ERR_LAUNCH;
-    if (lr2_allow_dynamic_lds(gemm256_mx_kernel<4, false>, LDS_BYTES, "gemm256_mx")) return LR2_ERR_LAUNCH;
-    if (lr2_allow_dynamic_lds(gemm256_mx_kernel<8, false>, LDS_BYTES, "gemm256_mx")) return LR2_ERR_LAUNCH;
-    const char* e = getenv("LR2_MX_ABLATE");      // diagnostics only (wrong results): see k_step
-    abl = e ? atoi(e) : 0;
-    const char* e16 = getenv("LR2_MX_SC16");      // 0: one 4-byte scale gather per K step everywhere (A/B)
-    sc16_env = e16 ? atoi(e16) : 1;
+    if (lr2_allow_dynamic_lds(gemm256_mx_kernel<false>, LDS_BYTES, "gemm256_mx")) return LR2_ERR_LAUNCH;
+    if (lr2_allow_dynamic_lds(gemm256_mx_kernel<true>, LDS_BYTES16, "gemm256_mx")) return LR2_ERR_LAUNCH;
     attr_set = true;
   }
   const dim3 grid(tiles_m * tiles_n);
   // whole 16-byte scale chunks per row (K / 32 a multiple of 16): the SC16 form; else the 4-byte form
   // (from K = 2048: at K = 1024 -- 8 steps -- the row gather in the prologue costs more than the seven later gathers it saves)
-  const bool sc16 = sc16_env && (p.K % 512) == 0 && p.K >= 2048;
-  if (abl == 1) LR2_LAUNCH((gemm256_mx_kernel<1, false>), grid, dim3(512), LDS_BYTES, stream, p, tiles_m, tiles_n);
-  else if (abl == 2) LR2_LAUNCH((gemm256_mx_kernel<2, false>), grid, dim3(512), LDS_BYTES, stream, p, tiles_m, tiles_n);
-  else if (abl == 4) LR2_LAUNCH((gemm256_mx_kernel<4, false>), grid, dim3(512), LDS_BYTES, stream, p, tiles_m, tiles_n);
-  else if (abl == 8) LR2_LAUNCH((gemm256_mx_kernel<8, false>), grid, dim3(512), LDS_BYTES, stream, p, tiles_m, tiles_n);
-  else if (sc16) LR2_LAUNCH((gemm256_mx_kernel<0, true>), grid, dim3(512), LDS_BYTES16, stream, p, tiles_m, tiles_n);
-  else LR2_LAUNCH((gemm256_mx_kernel<0, false>), grid, dim3(512), LDS_BYTES, stream, p, tiles_m, tiles_n);
+  const bool sc16 = (p.K % 512) == 0 && p.K >= 2048;
+  if (sc16) LR2_LAUNCH(gemm256_mx_kernel<true>, grid, dim3(512), LDS_BYTES16, stream, p, tiles_m, tiles_n);
+  else LR2_LAUNCH(gemm256_mx_kernel<false>, grid, dim3(512), LDS_BYTES, stream, p, tiles_m, tiles_n);
   return lr2_launch_status(__func__);
 }

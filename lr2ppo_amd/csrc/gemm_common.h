@@ -21,10 +21,10 @@ struct GemmParams {
   int tiles_m, tiles_n;         // output tile grid
   int splits;                   // split-K factor (grid = tiles_m * tiles_n * splits workgroups, 1-D)
   float* partial;               // split-K workspace [splits][M][N] or nullptr
-  int dma_stages;               // LDS images per planes operand: 2 = double buffered (1 workgroup/CU at BM=128), 1 = single
-  int waves8;                   // planes x planes, 128 x 128 tiles: 8-wave workgroups (wave tile 64 x 32)
-  int ablate;                   // diagnostics only (LR2_GEMM_ABLATE): 2 no global loads, 4 no LDS fill
-  int strip_n;                  // tiles per strip along N of the XCD-aware tile order (0 = 8; LR2_GEMM_STRIP: an A/B switch of the 256 x 256 NT kernel)
+  int dma_stages;               // LDS images per planes operand: 2 = double buffered (the 32-deep tiles), 1 = single.  launch() sets it
+                                // from BK; a kernel argument because gemm_kernel's compile-time form of it needs more VGPRs (the 64-row
+                                // planes kernels: 128 -> 140, one wave per SIMD less)
+  bool epi_general;             // every slab through the general per-element epilogue (LR2_GEMM_EPI_GENERAL=1: the reference of the fast forms)
   Epilogue epi;
 };
 
@@ -46,9 +46,9 @@ __device__ __forceinline__ int xcd_chunk_index(int T, int bid) {
   const int q = T >> 3, r = T & 7, xcd = bid & 7, local = bid >> 3;
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
 }
-__device__ __forceinline__ void tile_coords(int tiles_m, int tiles_n, int bid, int& tm, int& tn, int strip = 8) {
+__device__ __forceinline__ void tile_coords(int tiles_m, int tiles_n, int bid, int& tm, int& tn) {
   const int i = xcd_chunk_index(tiles_m * tiles_n, bid);
-  const int SN = tiles_n < strip ? tiles_n : strip;
+  const int SN = tiles_n < 8 ? tiles_n : 8;
   const int full = (tiles_n / SN) * tiles_m * SN;  // tiles inside full-width strips
   if (i < full) {
     const int strip = i / (tiles_m * SN), rem = i % (tiles_m * SN);
@@ -352,8 +352,8 @@ __device__ __forceinline__ void epilogue_from_slab(const GemmParams& g, float* s
   slab_read_all<WN, NP, 0>(lds_addr(slab) + (uint32_t)((row0 * LDW + col) * 4), v);   // one row segment of 4 columns per lane
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_sched_barrier(0);
-  // (LR2_GEMM_ABLATE & 256 switches the fast forms off: tools/dbg/fuzz_epilogue.py compares the two paths bit for bit)
-  if (!partial && !(g.ablate & 256) && mw + 32 * HALF + 32 <= g.M && nw + WN <= g.N) {   // wave-uniform: the slab lies inside the matrix
+  // (LR2_GEMM_EPI_GENERAL=1 switches the fast forms off: tools/dbg/fuzz_epilogue.py compares the two paths bit for bit)
+  if (!partial && !g.epi_general && mw + 32 * HALF + 32 <= g.M && nw + WN <= g.N) {   // wave-uniform: the slab lies inside the matrix
     if (epilogue_fast_dispatch<NP, RPP, NS, WIDE>(g.epi, v, bias4, S.L, mw + 32 * HALF + row0, n, g.N)) return;
   }
 #pragma unroll
@@ -400,7 +400,7 @@ __device__ __forceinline__ void epilogue_wave(const GemmParams& g, f32x4_t (&acc
   // The wait for the bias load belongs HERE, once, in code every lane passes.  Without this use the first reads of bias4 sit
   // inside the slabs' range-checked (exec-masked) blocks, none of which dominates the next, so the compiler waits before each of
   // them -- and with loads and stores on one in-order counter the only wait it can write there is vmcnt(0): every slab waited for
-  // the stores of the slab before it, one HBM write latency each (12 us of a 67-us K = 768 tile, tools/dbg/tile_contention.py).
+  // the stores of the slab before it, one HBM write latency each (12 us of a 67-us K = 768 tile, profiles/experiments/README.md E).
   asm volatile("" ::"v"(bias4.x), "v"(bias4.y), "v"(bias4.z), "v"(bias4.w));
   epilogue_pipeline<WM, WN, MI, NI, NS, 0, PIPE, WIDE>(g, acc, slab, mw, nw, lane, partial, bias4, first);
 }

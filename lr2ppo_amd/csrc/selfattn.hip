@@ -13,17 +13,12 @@
 // contraction index permuted (slot (g, j) <-> key 4g + j for j < 4, 16 + 4g + j - 4 otherwise); the V fragments are read
 // with the same permutation by two ds_read_b64_tr_b16 (rows 4g .. 4g+3 and 16 + 4g .. 16 + 4g + 3 of the key block).
 // P never touches LDS and no shuffle is needed between the two GEMMs.
-#include <stdlib.h>
 
 #include "common.h"
 #include "lr2ppo_hip.h"
 
 namespace {
 
-#ifndef LR2_SA_ABLATE
-#define LR2_SA_ABLATE 0         // diagnostics (tools/dbg/attn_ablate.py builds variants of this file): bit 1 no K / V global loads, 2 no
-#endif                          // sub-tile work, 4 no softmax arithmetic, 8 no lo split of P, 16 no P V product, 32 no S product, 64 no store,
-                                // 128 no fragment loads of the persistent backward's compute waves (bits 1, 64, 128 apply to the backward)
 constexpr int HD = 64;          // head dim
 constexpr int ROW_B = HD * 2;   // bytes of one K / V row in one LDS plane
 constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
@@ -114,9 +109,8 @@ __device__ __forceinline__ void attn_phase_a(const char* sK, const float* sMask,
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
     f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
-    if (LR2_SA_ABLATE & 32) acc = f32x4_t{__builtin_bit_cast(float, (int)qh[0][0]), 0.f, (float)t, 0.f};
 #pragma unroll
-    for (int ks = 0; ks < ((LR2_SA_ABLATE & 32) ? 0 : 2); ++ks) {
+    for (int ks = 0; ks < 2; ++ks) {
       // A fragment: key row 16t + (l & 15), hd 8g + 32ks ..: k_off(16t + qn, g + 4ks) = 2048 t + k_off(qn, g + 4ks)
       const bf16x8_t kh = lds_ld16(kb[ks] + 2048 * t);
       const bf16x8_t kl = lds_ld16(kb[ks] + 2048 * t + PLANE);
@@ -142,7 +136,6 @@ __device__ __forceinline__ void attn_phase_a(const char* sK, const float* sMask,
   mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
   mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
   float sum = 0.f;
-  if (!(LR2_SA_ABLATE & 4)) {
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
 #pragma unroll
@@ -153,7 +146,6 @@ __device__ __forceinline__ void attn_phase_a(const char* sK, const float* sMask,
   }
   sum += __shfl_xor(sum, 16, 64);
   sum += __shfl_xor(sum, 32, 64);
-  } else sum = 1.0f + mx * 1e-30f;
   inv = 1.0f / sum;
   if (lse && g == 0 && q_row < L) lse[((size_t)b * heads + h) * L + q_row] = mx * LN2 + logf(sum);
   const uint64_t drow = (((uint64_t)b * heads + h) * L + (uint64_t)(q_row < L ? q_row : 0)) * mask_pitch(L);
@@ -179,7 +171,7 @@ __device__ __forceinline__ void attn_phase_a(const char* sK, const float* sMask,
     const uint32_t l45 = cvt_pk_bf16(p[4] - __uint_as_float(h45 << 16), p[5] - __uint_as_float(h45 & 0xffff0000u));
     const uint32_t l67 = cvt_pk_bf16(p[6] - __uint_as_float(h67 << 16), p[7] - __uint_as_float(h67 & 0xffff0000u));
     ph[u] = __builtin_bit_cast(bf16x8_t, (u32x4_t{h01, h23, h45, h67}));
-    pl[u] = (LR2_SA_ABLATE & 8) ? ph[u] : __builtin_bit_cast(bf16x8_t, (u32x4_t{l01, l23, l45, l67}));
+    pl[u] = __builtin_bit_cast(bf16x8_t, (u32x4_t{l01, l23, l45, l67}));
   }
 }
 
@@ -230,7 +222,7 @@ __device__ __forceinline__ void attn_phase_b(const char* sV, float* slab, const 
       for (int pass = 0; pass < 2; ++pass) {
         const int r = pass * 8 + (lane >> 3), c = (lane & 7) * 4;
         const int qr = sub * 16 + r;
-        if (qr < L && (!(LR2_SA_ABLATE & 64) || slab[r] == 12345.f)) {
+        if (qr < L) {
           const float4 v = *reinterpret_cast<const float4*>(slab + r * (32 + 4) + c);
           // uniform 64-bit base + 32-bit lane offset: the stores take the scalar-base form (no 64-bit address registers per lane)
           const size_t ubase = row0 * (size_t)ld_o + col0 + 32 * half;
@@ -249,10 +241,6 @@ __device__ __forceinline__ void attn_phase_b(const char* sV, float* slab, const 
   for (int n = 0; n < 4; ++n) o[n] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int u = 0; u < NT / 2; ++u) {
-    if (LR2_SA_ABLATE & 16) {
-      o[u & 3][0] += __builtin_bit_cast(float, (int)ph[u][0]) + __builtin_bit_cast(float, (int)pl[u][1]);
-      continue;
-    }
 #pragma unroll
     for (int n = 0; n < 4; ++n) {
       const bf16x8_t vh = lds_tr_pair(vb[n] + 4096 * u, vb[n] + 4096 * u + 2048);
@@ -277,7 +265,7 @@ __device__ __forceinline__ void attn_phase_b(const char* sV, float* slab, const 
   for (int pass = 0; pass < 4; ++pass) {
     const int r = pass * 4 + (lane >> 4), c = (lane & 15) * 4;
     const int qr = sub * 16 + r;
-    if (qr < L && (!(LR2_SA_ABLATE & 64) || slab[r] == 12345.f)) {
+    if (qr < L) {
       const float4 v = *reinterpret_cast<const float4*>(slab + r * (HD + 4) + c);
       const size_t off = (row0 + qr) * (size_t)ld_o + col0 + c;
       if (O) *reinterpret_cast<float4*>(O + off) = v;
@@ -352,7 +340,7 @@ __global__ __launch_bounds__(64 * NW) void self_attn_mfma_kernel(const bf16_t* _
       const int r = i >> 3, u = i & 7;
       kh[it] = u32x4_t{0, 0, 0, 0};
       kl[it] = kh[it]; vh[it] = kh[it]; vl[it] = kh[it];
-      if (i < LP * 8 && r < L && !(LR2_SA_ABLATE & 1)) {
+      if (i < LP * 8 && r < L) {
         const size_t o = (row0 + r) * (size_t)ld + col0 + u * 8;
         kh[it] = *reinterpret_cast<const u32x4_t*>(Kh + o);
         kl[it] = *reinterpret_cast<const u32x4_t*>(Kh + o + lo_off);
@@ -378,7 +366,7 @@ __global__ __launch_bounds__(64 * NW) void self_attn_mfma_kernel(const bf16_t* _
 
   __syncthreads();
   // K / V stay resident; each wave walks over 16-query sub-tiles (blockIdx.x strides them when the grid splits the queries)
-  for (int sub = sub_first; sub < ((LR2_SA_ABLATE & 2) ? 0 : n_sub); sub += sub_step) {
+  for (int sub = sub_first; sub < n_sub; sub += sub_step) {
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks) { qh[ks] = qh_next[ks]; ql[ks] = ql_next[ks]; }
   load_q(sub + sub_step, qh_next, ql_next);     // next sub-tile's queries travel while this one is computed
@@ -391,7 +379,7 @@ __global__ __launch_bounds__(64 * NW) void self_attn_mfma_kernel(const bf16_t* _
 // ---- persistent forward: one workgroup per CU walks over (sequence, head) pairs, K / V travel by LDS-DMA under the compute ----
 // The one-pair kernel above spends a quarter of its time waiting for its K / V planes (112 KiB per workgroup, one workgroup per CU:
 // nothing else runs meanwhile), every workgroup pays its launch and the drain of its last stores, and its phases (staging, S,
-// softmax, P V, stores) barely overlap: two waves per SIMD in the same phase (tools/dbg/attn_ablate.py).  Here
+// softmax, P V, stores) barely overlap: two waves per SIMD in the same phase (measured by ablation, profiles/experiments/README.md).  Here
 //   * a workgroup is 16 waves at <= 128 VGPRs: wave w < n_sub owns the 16-query sub-tile w of every pair (n_sub <= 14: L <= 224), waves
 //     14 and 15 only move data -- three to four waves per SIMD in different places instead of two in the same one;
 //   * a pair is two phases that touch different planes -- A: S = Q K^T + softmax (K, mask), the probabilities kept as bf16 fragments in
@@ -417,7 +405,7 @@ __device__ __forceinline__ void dma_head_rows(const __amdgpu_buffer_rsrc_t& hi, 
                                               int j0, int jstep, uint32_t pair_off, uint32_t row_bytes, int L) {
   constexpr int LP = 16 * NT, PLANE = LP * ROW_B;
   const int rl = lane >> 3, sl = lane & 7;
-  for (int j = j0; j < ((LR2_SA_ABLATE & 1) ? 0 : LP / 8); j += jstep) {
+  for (int j = j0; j < LP / 8; j += jstep) {
     const int r = 8 * j + rl;
     const int u = IS_V ? (sl ^ (((r >> 1) & 3) << 1)) : (sl ^ ((r >> 1) & 7));
     const uint32_t v = r < L ? pair_off + (uint32_t)r * row_bytes + (uint32_t)u * 16u : 0xFFFFFF00u;
@@ -547,7 +535,7 @@ __global__ __launch_bounds__(64 * PS_WAVES) void self_attn_persist_kernel(const 
     const float* mask = sMask + (it & 1) * LP;
     bf16x8_t ph[NT / 2], pl[NT / 2];
     float inv = 0.f;
-    if (!(LR2_SA_ABLATE & 2)) attn_phase_a<NT, DROP>(sK, mask, qh, ql, sub, opaque(lane), L, b, h, heads, scale, lse, dr, ph, pl, inv);
+    attn_phase_a<NT, DROP>(sK, mask, qh, ql, sub, opaque(lane), L, b, h, heads, scale, lse, dr, ph, pl, inv);
     phase_barrier();
     const int pn = p + gridDim.x;
     const bool more = pn < n_pairs;
@@ -556,7 +544,7 @@ __global__ __launch_bounds__(64 * PS_WAVES) void self_attn_persist_kernel(const 
     // the next pair's queries are requested once the probability registers are dead; they travel under the output's stores and the
     // wait at the barrier
     auto next_q = [&]() { if (more) load_q(row0n, hn * HD, qh, ql); };
-    if (!(LR2_SA_ABLATE & 2)) attn_phase_b<NT, true>(sV, slab, ph, pl, inv, sub, opaque(lane), L, row0, col0, O, Oh, o_lo_off, ld_o, next_q);
+    attn_phase_b<NT, true>(sV, slab, ph, pl, inv, sub, opaque(lane), L, row0, col0, O, Oh, o_lo_off, ld_o, next_q);
     if (!more) break;
     phase_barrier();
     p = pn; b = bn; h = hn; row0 = row0n; col0 = hn * HD;
@@ -1138,7 +1126,7 @@ __device__ __forceinline__ void dma_rows_k(const __amdgpu_buffer_rsrc_t& hi, con
                                            int j_begin, int j_end, int jstep, uint32_t pair_off, uint32_t row_bytes, int L) {
   constexpr int LP = 16 * NT, PLANE = LP * ROW_B;
   const int rl = lane >> 3, sl = lane & 7;
-  for (int j = j_begin; j < ((LR2_SA_ABLATE & 1) ? 0 : j_end); j += jstep) {
+  for (int j = j_begin; j < j_end; j += jstep) {
     const int r = 8 * j + rl;
     const int u = sl ^ d_swz(r);
     const uint32_t v = r < L ? pair_off + (uint32_t)r * row_bytes + (uint32_t)u * 16u : 0xFFFFFF00u;
@@ -1179,7 +1167,7 @@ __device__ __forceinline__ void store_tile_planes_half(const f32x4_t (&o)[4], fl
 #pragma unroll
     for (int pass = 0; pass < 2; ++pass) {
       const int r = pass * 8 + (lane >> 3), c = (lane & 7) * 4;
-      if (row_first + r < rows_valid && (!(LR2_SA_ABLATE & 64) || slab[r] == 12345.f)) {
+      if (row_first + r < rows_valid) {
         const float4 v = *reinterpret_cast<const float4*>(slab + r * (32 + 4) + c);
         store_planes4(dst_hi + base + 32 * half + ((uint32_t)(row_first + r) * (uint32_t)row_stride + (uint32_t)c), lo_off, v);
       }
@@ -1318,10 +1306,9 @@ __global__ __launch_bounds__(64 * PS_WAVES) void self_attn_bwd_dq_persist_kernel
     const size_t row0_ = (size_t)b * L;
     const uint32_t lr = (uint32_t)(q_ok ? q_row : 0);
     bf16x8_t oh[2], ol[2];
-    const bool ld_ok = q_ok && !(LR2_SA_ABLATE & 128);
-    load_frags_u(A.q + row0_ * (size_t)A.ld + h * HD, A.lo_off, lr * (uint32_t)A.ld + 8u * g, ld_ok, qh, ql);
-    load_frags_u(A.go + row0_ * (size_t)A.ld_do + h * HD, A.do_lo_off, lr * (uint32_t)A.ld_do + 8u * g, ld_ok, gh, gl);
-    load_frags_u(A.o + row0_ * (size_t)A.ld_o + h * HD, A.o_lo_off, lr * (uint32_t)A.ld_o + 8u * g, ld_ok, oh, ol);
+    load_frags_u(A.q + row0_ * (size_t)A.ld + h * HD, A.lo_off, lr * (uint32_t)A.ld + 8u * g, q_ok, qh, ql);
+    load_frags_u(A.go + row0_ * (size_t)A.ld_do + h * HD, A.do_lo_off, lr * (uint32_t)A.ld_do + 8u * g, q_ok, gh, gl);
+    load_frags_u(A.o + row0_ * (size_t)A.ld_o + h * HD, A.o_lo_off, lr * (uint32_t)A.ld_o + 8u * g, q_ok, oh, ol);
     const size_t si0 = (size_t)pp * L;
     lse2 = q_ok ? A.lse[si0 + lr] * LOG2E : 0.f;
     float d = frag_dot(gh[0], gl[0], oh[0], ol[0]) + frag_dot(gh[1], gl[1], oh[1], ol[1]);
@@ -1516,9 +1503,8 @@ __global__ __launch_bounds__(64 * PS_WAVES) void self_attn_bwd_dkv_persist_kerne
     const int key_ = sub * 16 + (lane_ & 15);
     const bool ok_ = key_ < L;
     const uint32_t lr = (uint32_t)(ok_ ? key_ : 0), lo8 = 8u * (uint32_t)(lane_ >> 4);
-    const bool ld_ok = ok_ && !(LR2_SA_ABLATE & 128);
-    load_frags_u(A.k + row0_ * (size_t)A.ld + h * HD, A.lo_off, lr * (uint32_t)A.ld + lo8, ld_ok, kh, kl);
-    load_frags_u(A.v + row0_ * (size_t)A.ld + h * HD, A.lo_off, lr * (uint32_t)A.ld + lo8, ld_ok, vh, vl);
+    load_frags_u(A.k + row0_ * (size_t)A.ld + h * HD, A.lo_off, lr * (uint32_t)A.ld + lo8, ok_, kh, kl);
+    load_frags_u(A.v + row0_ * (size_t)A.ld + h * HD, A.lo_off, lr * (uint32_t)A.ld + lo8, ok_, vh, vl);
     kmask2 = ok_ ? ((A.seg[row0_ + lr] > 0) ? 0.f : -10000.0f * LOG2E) : -INFINITY;
   };
   fetch(p);
@@ -1892,7 +1878,6 @@ struct AttnArgs {
 
 // Forward: 8 waves per workgroup (2 per SIMD) hide the LDS-read latency of the dependent tile chains; the 256-key
 // variant keeps 4 (its K/V planes + 8 output slabs would not fit the 160 KiB of LDS).
-static bool attn_persist_enabled();
 static int cu_count() {
   static int n = 0;
   if (n == 0) {
@@ -1903,8 +1888,7 @@ static int cu_count() {
   return n;
 }
 
-// The persistent form: at least one pair per CU, every operand offset a 32-bit byte count (LR2_ATTN_PERSIST=0: an A/B switch, read
-// once per process).
+// The persistent form: at least one pair per CU, every operand offset a 32-bit byte count.
 template <int NT>
 int launch_fwd_persist(const AttnArgs& a, float* o, bf16_t* oh, size_t o_lo_off, int ld_o, float* lse, uint32_t kv_bytes) {
   constexpr int LP = 16 * NT;
@@ -1929,10 +1913,9 @@ int launch_fwd(const AttnArgs& a, float* o, bf16_t* oh, size_t o_lo_off, int ld_
   constexpr int LP = 16 * NT;
   constexpr int NW = NT <= 14 ? 8 : 4;
   if constexpr (NT <= 14) {
-    const bool persist_on = attn_persist_enabled();
     // bytes a K / V descriptor spans from its first element: the last row's head columns end (rows - 1) * ld + heads * 64 elements on
     const uint64_t span = ((uint64_t)a.batch * a.L - 1) * (uint64_t)a.ld * 2u + (uint64_t)a.heads * HD * 2u;
-    if (persist_on && a.batch * a.heads >= cu_count() && (a.L + 15) / 16 <= PS_MAX_SUB && span < 0xFFFFFF00ull)
+    if (a.batch * a.heads >= cu_count() && (a.L + 15) / 16 <= PS_MAX_SUB && span < 0xFFFFFF00ull)
       return launch_fwd_persist<NT>(a, o, oh, o_lo_off, ld_o, lse, (uint32_t)span);
   }
   const size_t lds = (size_t)4 * LP * ROW_B + (size_t)LP * 4 + (size_t)NW * 16 * (HD + 4) * 4;
@@ -1977,15 +1960,11 @@ static int fwd_blocked_dispatch(const AttnArgs& a, float* o, bf16_t* oh, size_t 
 }
 
 // The backward's persistent form needs the forward's output and log-sum-exp (o != nullptr: lse is then an INPUT), at least one pair per
-// CU, 32-bit byte offsets into every operand.  (LR2_ATTN_PERSIST=0: the A/B switch of the forward applies here too.)
-static bool attn_persist_enabled() {
-  static const bool on = !(getenv("LR2_ATTN_PERSIST") && atoi(getenv("LR2_ATTN_PERSIST")) == 0);
-  return on;
-}
+// CU, 32-bit byte offsets into every operand.
 static bool bwd_persist_ok(int batch, int heads, int L, int ld, int ld_do, bool has_o) {
   const uint64_t span = ((uint64_t)batch * L - 1) * (uint64_t)ld * 2u + (uint64_t)heads * HD * 2u;
   const uint64_t span_do = ((uint64_t)batch * L - 1) * (uint64_t)ld_do * 2u + (uint64_t)heads * HD * 2u;
-  return attn_persist_enabled() && has_o && L <= 16 * PS_MAX_SUB && batch * heads >= cu_count() && span < 0xFFFFFF00ull &&
+  return has_o && L <= 16 * PS_MAX_SUB && batch * heads >= cu_count() && span < 0xFFFFFF00ull &&
          span_do < 0xFFFFFF00ull;
 }
 
@@ -2237,14 +2216,14 @@ extern "C" int lr2_self_attn_bwd(const void* q_hi, const void* k_hi, const void*
 #undef CALL
 }
 
-// Which form of the attention kernels a call of this shape runs (a pure function of the shape, the device's CU count and
-// LR2_ATTN_PERSIST): *fwd_persistent / *bwd_persistent = 1 when lr2_self_attn_fwd / lr2_self_attn_bwd (the latter given o_hi) take the
+// Which form of the attention kernels a call of this shape runs (a pure function of the shape and the device's CU count):
+// *fwd_persistent / *bwd_persistent = 1 when lr2_self_attn_fwd / lr2_self_attn_bwd (the latter given o_hi) take the
 // persistent kernels.  Tests assert on it; ld / ld_do as in the calls.
 extern "C" int lr2_self_attn_plan(int batch, int heads, int L, int ld, int ld_do, int* fwd_persistent, int* bwd_persistent) {
   if (batch <= 0 || heads <= 0 || L < 1) return LR2_ERR_ARG;
   const uint64_t span = ((uint64_t)batch * L - 1) * (uint64_t)ld * 2u + (uint64_t)heads * HD * 2u;
   if (fwd_persistent)
-    *fwd_persistent = attn_persist_enabled() && L <= 16 * PS_MAX_SUB && batch * heads >= cu_count() && span < 0xFFFFFF00ull;
+    *fwd_persistent = L <= 16 * PS_MAX_SUB && batch * heads >= cu_count() && span < 0xFFFFFF00ull;
   if (bwd_persistent) *bwd_persistent = bwd_persist_ok(batch, heads, L, ld, ld_do, true);
   return 0;
 }

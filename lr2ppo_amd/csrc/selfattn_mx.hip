@@ -12,7 +12,6 @@
 // fragments, V for ds_read_b64_tr_b16); each wave walks over 16-query sub-tiles: S^T = K Q^T (2 MFMAs per 16 keys), softmax in the
 // log2 domain across the 4 lanes that share a query, P as bf16 straight from the accumulators, O = P V (4 MFMAs per 32 keys),
 // 1 / sum on the 16 outputs, rows through the wave's LDS slab -> fp32 and / or MX-FP8.
-#include <stdlib.h>
 
 #include "common.h"
 #include "lr2ppo_hip.h"
@@ -486,10 +485,9 @@ template <int NT>
 int launch(const bf16_t* q, const bf16_t* k, const bf16_t* v, int ld, const int64_t* seg, float* of, uint8_t* oq, uint8_t* os, int ld_o,
            int batch, int heads, int L, float scale, hipStream_t stream) {
   {
-    // the persistent form: at least one pair per CU, 32-bit byte offsets (LR2_ATTN_PERSIST=0: the A/B switch of selfattn.hip)
-    static const bool on = !(getenv("LR2_ATTN_PERSIST") && atoi(getenv("LR2_ATTN_PERSIST")) == 0);
+    // the persistent form: at least one pair per CU, 32-bit byte offsets
     const uint64_t span = ((uint64_t)batch * L - 1) * (uint64_t)ld * 2u + (uint64_t)heads * HD * 2u;
-    if (on && batch * heads >= mx_cu_count() && (L + 15) / 16 <= 2 * PM_COMPUTE && span < 0xFFFFFF00ull)
+    if (batch * heads >= mx_cu_count() && (L + 15) / 16 <= 2 * PM_COMPUTE && span < 0xFFFFFF00ull)
       return launch_persist<NT>(q, k, v, ld, seg, of, oq, os, ld_o, batch, heads, L, scale, (uint32_t)span, stream);
   }
   constexpr int LP = 16 * NT, NW = 8;

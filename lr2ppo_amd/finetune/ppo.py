@@ -883,7 +883,7 @@ def update_minibatch(args, model, optimizer, critic_optim, record, dp=None, inpu
     wa = dp.reduce_start(actor)            # overlaps the critic's backward
     with side.run():                       # the critic's backward, gradient exchange and optimizer step beside the actor's
         # (its out_layer.fc1 update first, the actor's last: the two HBM-bound passes fall beside the other model's GEMMs)
-        gc = critic.engine_backward(dvalue, dp, fc1_update=fc, fc1_early=side.on and os.environ.get("LR2_FC1_EARLY", "1") != "0",
+        gc = critic.engine_backward(dvalue, dp, fc1_update=fc, fc1_early=side.on,
                                     input_grads=input_grads)
         wc = dp.reduce_start(critic)
         if side.on:

@@ -273,7 +273,7 @@ def _use_gemm256(M: int, N: int, K: int, passes: int) -> bool:
     # round 4 (tools/dbg/rowsplit_ab.py): more than one round with a last round LESS than half full -- lr2_gemm then sends the rows of
     # the whole rounds to the 256 x 256 kernel and the remaining rows to the 128- / 64-row kernels (row split: two launches, no
     # reduction): M = 12544, N = 3072, K = 768 (588 tiles) 166 us against 199 (NN on 128-row tiles) / 184 (three rounds of 256 x 256)
-    if 256 < tiles < 5 * 256 and 0 < tiles % 256 < 128 and K % 64 == 0 and os.environ.get("LR2_GEMM_ROWSPLIT", "1") != "0":
+    if 256 < tiles < 5 * 256 and 0 < tiles % 256 < 128 and K % 64 == 0:
         return True
     # one partial round, long contraction (M = 12544, N = 768, K = 3072: 147 tiles): each CU runs one tile at the 256 x 256 kernel's
     # main-loop rate and the epilogue is amortised over 96 K steps -- 182 us against 197 (64-row tiles) / 212 (128-row), round 3;
@@ -282,9 +282,9 @@ def _use_gemm256(M: int, N: int, K: int, passes: int) -> bool:
         return True
     # round 4, late: the kernel's 192-row tile (gemm256.hip, MIH = 3; the launcher takes it when a round of 192-row tiles fills CUs a
     # round of 256-row tiles leaves idle): M = 12544, N = 768: 147 -> 198 workgroups -- K = 768: 50 us against 56 (64-row tiles),
-    # K = 1536: 80 against 94 (tools/dbg/gemm192_ab.py)
+    # K = 1536: 80 against 94 (profiles/experiments/README.md F.6)
     t192 = ((M + 191) // 192) * ((N + 255) // 256)
-    return tiles < 256 and 192 <= t192 <= 256 and t192 > tiles and K >= 768 and os.environ.get("LR2_GEMM_192", "1") != "0"
+    return tiles < 256 and 192 <= t192 <= 256 and t192 > tiles and K >= 768
 
 
 @functools.lru_cache(maxsize=4096)

@@ -142,7 +142,7 @@ def test_ring_product_matches_the_dequantised_operands(dev, M, N, K, act, with_r
     K steps per 16-byte DMA -- 1, 2, 3 and 5 such chunks per row; else one 4-byte gather per step), every K-step parity, ragged M (a last
     tile row of 64 / 1 rows), N a multiple of 128 but not of 256 (a half-empty last tile column), fused bias / GELU / residual --
     against the fp64 product of the dequantised operands (bound of the instruction's adder tree) and against the 128 x 128 kernel
-    (LR2_FP8_256=0 is read once per process, so the comparison value comes from a slice that stays on the small kernel)."""
+    (the comparison value comes from a slice that the size rule keeps on the small kernel)."""
     from lr2ppo_amd import ops
     from oracle import lr2ppo_oracle as O
     assert ((M + 255) // 256) * ((N + 255) // 256) >= 256

@@ -566,7 +566,7 @@ def test_vit_l14_full_depth_forward_and_gradients_match_oracle(dev):
 
 def test_gemm_epilogue_fast_forms_equal_the_general_path_bit_for_bit(dev):
     """Slabs inside the matrix take a straight-line form of the epilogue (gemm_common.h::epilogue_fast); slabs across the edge, and
-    every slab under LR2_GEMM_ABLATE=256, the per-element general path.  Same bits: 120 random products over every instantiated form
+    every slab under LR2_GEMM_EPI_GENERAL=1, the per-element general path.  Same bits: 120 random products over every instantiated form
     (and two that are not), both kernel families, run in two child processes and compared by hash."""
     import subprocess
     import sys

@@ -1,6 +1,6 @@
 """The GEMM epilogue's fast forms (gemm_common.h::epilogue_fast, taken by slabs that lie inside the matrix) against the general
 per-element path, BIT FOR BIT: the same random products -- every fast form, tiles inside and across the matrix edge, 128- and 256-row
-kernels, NT and NN -- run in two child processes, one with LR2_GEMM_ABLATE=256 (fast forms off); each prints a hash of everything
+kernels, NT and NN -- run in two child processes, one with LR2_GEMM_EPI_GENERAL=1 (fast forms off); each prints a hash of everything
 the product wrote (the general path itself is checked against fp64 by tools/dbg/fuzz_kernels.py and tests/test_kernels_gpu.py).  usage: python tools/dbg/fuzz_epilogue.py [--n 300] [--seed 0]"""
 import argparse
 import hashlib
@@ -71,13 +71,13 @@ def main():
     if a.child:
         return child(a.n, a.seed)
     outs = []
-    for ablate in ("0", "256"):
-        env = dict(os.environ, LR2_GEMM_ABLATE=ablate, PYTHONPATH=ROOT)
+    for general in ("0", "1"):
+        env = dict(os.environ, LR2_GEMM_EPI_GENERAL=general, PYTHONPATH=ROOT)
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--n", str(a.n), "--seed", str(a.seed)], env=env,
                            capture_output=True, text=True, timeout=1500)
         if r.returncode != 0:
             print(r.stdout[-2000:], r.stderr[-4000:])
-            raise SystemExit(f"child with LR2_GEMM_ABLATE={ablate} failed")
+            raise SystemExit(f"child with LR2_GEMM_EPI_GENERAL={general} failed")
         outs.append([l for l in r.stdout.splitlines() if l.startswith("case ")])
     diff = [(x, y) for x, y in zip(*outs) if x != y]
     for x, y in diff[:20]:
