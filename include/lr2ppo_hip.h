@@ -24,7 +24,7 @@ extern "C" {
 #define LR2_ERR_SHAPE (-2)  /* shape not supported by the kernel's tiling */
 #define LR2_ERR_LAUNCH (-3) /* HIP launch failure */
 
-#define LR2_ABI_VERSION 19
+#define LR2_ABI_VERSION 20
 int lr2_abi_version(void);
 /* Fills name[0..len) with the HIP device name and returns the CU count (or <0). */
 int lr2_device_info(char* name, int len);
@@ -385,6 +385,31 @@ int lr2_gemm_mxfp8(const void* a_q, const void* a_scales, const void* b_q, const
  * replaces: tencentpretrain/layers/multi_headed_attn.py:60-74 in that mode. */
 int lr2_self_attn_fwd_bf16(const void* q, const void* k, const void* v, int ld, const int64_t* seg, void* o_f32, void* o_q,
                            void* o_scales, int ld_o, int batch, int heads, int L, int head_dim, float scale, void* stream);
+
+/* ABI 20.  MX-FP8 encoder training (FeatureExtractor(precision="mxfp8_train")): the backward's operands, blocked along the axis its
+ * products reduce over, and a K-sliced weight-gradient product.
+ *   lr2_quant_mxfp8_t: x [rows, cols] -- fp32 (is_planes 0) or bf16 hi / lo planes with the lo plane lo_off elements behind (is_planes 1),
+ *                      row stride ldx -- through the prologue act (0: x; 1: GELU(x); 2: x * GELU'(z), z fp32 [rows, ld_z]) -> qt / st
+ *                      (both or neither): MX-FP8 of x^T, [cols, rows_pad] bytes + [cols, rows_pad / 32] scales (rows_pad = rows rounded
+ *                      up to 128, padding zero bytes); q / scales (both or neither; qt or q required): the row-blocked MX-FP8 of the same values, byte-identical to
+ *                      lr2_quant_mxfp8; colsum / partials (both or neither): fp32 column sums [cols] written (accumulate 0) or added
+ *                      (1), deterministic, through partials [rows_pad / 128, cols].  cols % 64 == 0; x, z, qt, q 16-byte aligned (planes:
+ *                      8-byte), else LR2_ERR_SHAPE.
+ * replaces: the split into bf16 planes of the backward's operands (lr2_split_planes / lr2_split_planes_t) and lr2_colsum, in that mode. */
+int lr2_quant_mxfp8_t(const void* x, int is_planes, uint64_t lo_off, int ldx, const void* z, int ld_z, int act, void* qt, void* st,
+                      void* q, void* scales, void* colsum, void* partials, int accumulate, int rows, int cols, void* stream);
+/*   lr2_gemm_mxfp8_wgrad: out[M, ld_out] (+)= A_q . B_q^T with A_q [M, K], B_q [N, K] as lr2_quant_mxfp8_t writes them (K = the padded
+ *                      token count); `splits` K slices (capped at K / 128) leave fp32 partials in workspace [splits, M, N] that one more
+ *                      launch sums in slice order: the same bits on every run.  splits == 1: no workspace.  M, N, K % 128 == 0;
+ *                      out and workspace 16-byte aligned.
+ * replaces: the TN weight-gradient products of planes (lr2_gemm with trans_a = trans_b = 1), in that mode. */
+int lr2_gemm_mxfp8_wgrad(const void* a_q, const void* a_scales, const void* b_q, const void* b_scales, void* out, int ld_out,
+                         int accumulate, void* workspace, int splits, int M, int N, int K, void* stream);
+/*   lr2_dropout_residual: out[n] = resid + dropout_mask(y) / (1 - p), the mask of lr2_dropout_apply (element index = flat index);
+ *                      y, resid, out 16-byte aligned.
+ * replaces: the fused dropout + residual epilogue of lr2_gemm behind an MX-FP8 product (dropout_1 / dropout_2 of a layer). */
+int lr2_dropout_residual(const void* y, const void* resid, void* out, uint64_t n, float drop_p, uint64_t drop_seed, uint32_t drop_site,
+                         void* stream);
 
 #ifdef __cplusplus
 }

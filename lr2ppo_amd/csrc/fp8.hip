@@ -62,14 +62,14 @@ __global__ __launch_bounds__(256) void quant_mxfp8_kernel(const float* __restric
 // and four of B per K step: requested from global memory before the step's matrix instructions, written to the other stage after.
 __device__ __forceinline__ int mx_off(int r, int c) { return r * 128 + ((c ^ (r & 7)) << 4); }
 
-__global__ __launch_bounds__(256, 2) void gemm_mxfp8_lds_kernel(Mx8Params p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+// The main loop of one 128 x 128 output tile (tm, tn) over K steps [k_begin, k_end) (multiples of 128): the four waves' 4 x 4 instruction
+// tiles accumulate into acc.  Shared by the one-pass product below and the K-sliced weight-gradient product.  Ends with a barrier.
+__device__ __forceinline__ void mx_tile_mainloop(const Mx8Params& p, int tm, int tn, int k_begin, int k_end, char* smem,
+                                                 f32x4_t (&acc)[4][4]) {
   char* sA = smem;                     // [2][128 * 128]
   char* sB = smem + 2 * 16384;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 1, wc = wave & 1;
-  const int tiles_n = p.N / 128;
-  const int tm = blockIdx.x / tiles_n, tn = blockIdx.x % tiles_n;
   const int r16 = lane & 15, q = lane >> 4;
   // this thread's four chunks of a stage: rows (tid >> 3) + 32 it, chunk tid & 7
   const int cr = tid >> 3, cc = tid & 7;
@@ -79,8 +79,8 @@ __global__ __launch_bounds__(256, 2) void gemm_mxfp8_lds_kernel(Mx8Params p) {
   for (int it = 0; it < 4; ++it) {
     int m = tm * 128 + cr + 32 * it;
     if (m >= p.M) m = p.M - 1;
-    ga[it] = p.aq + (size_t)m * p.K + 16 * cc;
-    gb[it] = p.bq + (size_t)(tn * 128 + cr + 32 * it) * p.K + 16 * cc;
+    ga[it] = p.aq + (size_t)m * p.K + k_begin + 16 * cc;
+    gb[it] = p.bq + (size_t)(tn * 128 + cr + 32 * it) * p.K + k_begin + 16 * cc;
   }
   const uint8_t* asrow[4];
   const uint8_t* bsrow[4];
@@ -88,14 +88,9 @@ __global__ __launch_bounds__(256, 2) void gemm_mxfp8_lds_kernel(Mx8Params p) {
   for (int i = 0; i < 4; ++i) {
     int m = tm * 128 + wr * 64 + 16 * i + r16;
     if (m >= p.M) m = p.M - 1;
-    asrow[i] = p.as + (size_t)m * (p.K / 32) + q;
-    bsrow[i] = p.bs + (size_t)(tn * 128 + wc * 64 + 16 * i + r16) * (p.K / 32) + q;
+    asrow[i] = p.as + (size_t)m * (p.K / 32) + (k_begin >> 5) + q;
+    bsrow[i] = p.bs + (size_t)(tn * 128 + wc * 64 + 16 * i + r16) * (p.K / 32) + (k_begin >> 5) + q;
   }
-  f32x4_t acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   v4i_t ra[4], rb[4];
 #pragma unroll
   for (int it = 0; it < 4; ++it) {
@@ -109,8 +104,8 @@ __global__ __launch_bounds__(256, 2) void gemm_mxfp8_lds_kernel(Mx8Params p) {
   }
   __syncthreads();
   int st = 0;
-  for (int k0 = 0; k0 < p.K; k0 += 128) {
-    const bool more = k0 + 128 < p.K;
+  for (int k0 = 0; k0 < k_end - k_begin; k0 += 128) {
+    const bool more = k0 + 128 < k_end - k_begin;
     if (more) {
 #pragma unroll
       for (int it = 0; it < 4; ++it) {
@@ -156,6 +151,21 @@ __global__ __launch_bounds__(256, 2) void gemm_mxfp8_lds_kernel(Mx8Params p) {
     __syncthreads();
     st ^= 1;
   }
+}
+
+__global__ __launch_bounds__(256, 2) void gemm_mxfp8_lds_kernel(Mx8Params p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wr = wave >> 1, wc = wave & 1;
+  const int tiles_n = p.N / 128;
+  const int tm = blockIdx.x / tiles_n, tn = blockIdx.x % tiles_n;
+  const int r16 = lane & 15, q = lane >> 4;
+  f32x4_t acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  mx_tile_mainloop(p, tm, tn, 0, p.K, smem, acc);
   // epilogue: the wave's 64 x 64 results through a wave-private LDS slab, 32 rows at a time (the operand stages are dead: the loop
   // ended with a barrier), so that a row leaves as 256 contiguous bytes instead of 16 four-byte pieces
   const int m0 = tm * 128 + wr * 64, n0 = tn * 128 + wc * 64;
@@ -219,6 +229,59 @@ __global__ __launch_bounds__(256, 2) void gemm_mxfp8_lds_kernel(Mx8Params p) {
   }
 }
 
+// ---- weight-gradient product, K-sliced: workgroup (tile, slice) runs K steps [slice * kper, min(K, (slice + 1) * kper)) of one 128 x 128
+// tile and stores its fp32 partial as it is (dst = the workspace slab of the slice, ld N), or, with one slice, the result itself
+// (dst = out, ld ld_out, + the old value when accumulating).  M % 128 == 0: every tile row exists.
+// The stores are single 4-byte lanes (16 consecutive floats = 64 bytes per row and instruction), not rows staged through LDS as in
+// gemm_mxfp8_lds_kernel: a slab is written once and read once by the reduction (8 B per output element and slice against K / 128
+// steps of main loop), and the one-slice form -- where the store pattern would matter -- is taken only on request (splits = 1;
+// mxfp8_wgrad_splits picks one slice only below 1024 tokens, where the whole product is a few microseconds). ----
+__global__ __launch_bounds__(256, 2) void gemm_mxfp8_wgrad_kernel(Mx8Params p, float* __restrict__ dst, int ld, int kper, int accumulate) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int wr = wave >> 1, wc = wave & 1;
+  const int tiles_n = p.N / 128;
+  const int tm = blockIdx.x / tiles_n, tn = blockIdx.x % tiles_n;
+  const int k_begin = blockIdx.y * kper, k_end = min(p.K, k_begin + kper);
+  f32x4_t acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  mx_tile_mainloop(p, tm, tn, k_begin, k_end, smem, acc);
+  float* slab = dst + (size_t)blockIdx.y * p.M * p.N;
+  const int m0 = tm * 128 + wr * 64 + 4 * (lane >> 4), n0 = tn * 128 + wc * 64 + (lane & 15);
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float* o = slab + (size_t)(m0 + 16 * i + r) * ld + n0 + 16 * j;
+        *o = accumulate ? *o + acc[i][j][r] : acc[i][j][r];
+      }
+}
+
+// out[m, n] (+)= sum of the slices' partials, slice 0 first: a fixed association, so the bits do not depend on timing
+__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ ws, float* __restrict__ out, int M, int N, int ld_out,
+                                                           int splits, int accumulate) {
+  const size_t n4 = (size_t)M * N / 4, slab = (size_t)M * N;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+    float4 s = reinterpret_cast<const float4*>(ws)[i];
+    for (int k = 1; k < splits; ++k) {
+      const float4 t = reinterpret_cast<const float4*>(ws + k * slab)[i];
+      s.x += t.x; s.y += t.y; s.z += t.z; s.w += t.w;
+    }
+    const int m = (int)(4 * i / N), n = (int)(4 * i % N);
+    float4* o = reinterpret_cast<float4*>(out + (size_t)m * ld_out + n);
+    if (accumulate) {
+      const float4 v = *o;
+      s = make_float4(v.x + s.x, v.y + s.y, v.z + s.z, v.w + s.w);
+    }
+    *o = s;
+  }
+}
+
 }  // namespace
 
 extern "C" int lr2_quant_mxfp8(const void* x, int ldx, void* q, void* scales, int rows, int K, void* stream) {
@@ -256,5 +319,37 @@ extern "C" int lr2_gemm_mxfp8(const void* a_q, const void* a_scales, const void*
     attr = true;
   }
   LR2_LAUNCH(gemm_mxfp8_lds_kernel, dim3(tiles), dim3(256), 65536, (hipStream_t)stream, p);
+  return lr2_launch_status(__func__);
+}
+
+extern "C" int lr2_gemm_mxfp8_wgrad(const void* a_q, const void* a_scales, const void* b_q, const void* b_scales, void* out, int ld_out,
+                                    int accumulate, void* workspace, int splits, int M, int N, int K, void* stream) {
+  if (!a_q || !a_scales || !b_q || !b_scales || !out || M <= 0 || N <= 0 || K <= 0 || splits < 1 || (accumulate != 0 && accumulate != 1))
+    return LR2_ERR_ARG;
+  if (M % 128 || N % 128 || K % 128 || ld_out < N || ld_out % 4) return LR2_ERR_SHAPE;
+  if ((uintptr_t)out % 16 || (uintptr_t)workspace % 16) return LR2_ERR_SHAPE;         // the reduction's float4 accesses
+  const int steps = K / 128;
+  if (splits > steps) splits = steps;
+  const int kper = 128 * ((steps + splits - 1) / splits);
+  splits = (K + kper - 1) / kper;                      // every slice non-empty
+  if (splits > 1 && !workspace) return LR2_ERR_ARG;
+  static bool attr = false;
+  if (!attr) {
+    if (lr2_allow_dynamic_lds(gemm_mxfp8_wgrad_kernel, 65536, "gemm_mxfp8_wgrad")) return LR2_ERR_LAUNCH;
+    attr = true;
+  }
+  Mx8Params p{(const uint8_t*)a_q, (const uint8_t*)a_scales, (const uint8_t*)b_q, (const uint8_t*)b_scales, nullptr, nullptr, nullptr,
+              M, N, K, N, 0, 0, nullptr, nullptr, nullptr, 0, 0};
+  const int tiles = (M / 128) * (N / 128);
+  if (splits == 1) {
+    LR2_LAUNCH(gemm_mxfp8_wgrad_kernel, dim3(tiles, 1), dim3(256), 65536, (hipStream_t)stream, p, (float*)out, ld_out, kper, accumulate);
+    return lr2_launch_status(__func__);
+  }
+  LR2_LAUNCH(gemm_mxfp8_wgrad_kernel, dim3(tiles, splits), dim3(256), 65536, (hipStream_t)stream, p, (float*)workspace, N, kper, 0);
+  if (lr2_launch_status(__func__)) return LR2_ERR_LAUNCH;
+  size_t blocks = ((size_t)M * N / 4 + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  LR2_LAUNCH(wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, (float*)out, M, N,
+             ld_out, splits, accumulate);
   return lr2_launch_status(__func__);
 }

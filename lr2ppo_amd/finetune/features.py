@@ -20,7 +20,8 @@ An image tower wider than the heads' feature width (BASELINE.json configs[4]: Vi
 hard-code 768: finetune/ppo.py:202-208,219-220) ends in a `VisualProjection` -- the bias-free `[hidden_img -> visual_feat_dim]`
 map CLIP applies to its pooled [CLS] row (`x = ln_post(x[:, 0, :]) @ proj`, the `encode_image` preprocess.py:59-61,83 calls to make
 the reference's img_emb); absent when the widths agree.  `precision="mxfp8"` routes both stacks through the MX-FP8 products of
-csrc/fp8.hip (inference only; the parity path stays split-bf16).
+csrc/fp8.hip (inference only; the parity path stays split-bf16); `precision="mxfp8_train"` fine-tunes them with MX-FP8 products
+forward and backward (csrc/fp8_train.hip).
 """
 from __future__ import annotations
 
@@ -152,9 +153,11 @@ class FeatureExtractor(nn.Module):
     with `load_pretrained`.  feat_dim: the width of both outputs = the heads' `visual_feat_dim` (default: the text stack's hidden
     size); an image tower of another width gets `visual_projection` (VisualProjection) behind its pooled row.
     precision: "split_bf16" (default: the fp32-grade parity path) or "mxfp8" -- extract() / no-grad forward() run every
-    projection of both stacks as an MX-FP8 product (TransformerEncoder.forward_fp8); training paths refuse that mode."""
+    projection of both stacks as an MX-FP8 product (TransformerEncoder.forward_fp8); training paths refuse that mode -- or
+    "mxfp8_train": fine-tuning in MX-FP8, every projection's forward, input gradient and weight gradient an MX-FP8 product
+    (TransformerEncoder._forward_train_fp8 / _backward_train_fp8) on every route, extract() included (that forward, dropout off)."""
 
-    PRECISIONS = ("split_bf16", "mxfp8")
+    PRECISIONS = ("split_bf16", "mxfp8", "mxfp8_train")
 
     def __init__(self, vit_args: Optional[argparse.Namespace] = None, text_args: Optional[argparse.Namespace] = None,
                  vocab_size: int = ROBERTA_VOCAB, seq_length: int = 196, feat_dim: Optional[int] = None,
@@ -175,6 +178,7 @@ class FeatureExtractor(nn.Module):
         self.visual_projection = (VisualProjection(self.vit_args.hidden_size, self.feat_dim)
                                   if self.vit_args.hidden_size != self.feat_dim else None)
         self.text.embedding.defer_id_check = True          # one check per extract() at its end, not one sync per call
+        self.image.encoder.fp8_train = self.text.encoder.fp8_train = precision == "mxfp8_train"
 
     def load_pretrained(self, vit_path: Optional[str] = None, text_path: Optional[str] = None):
         """Released TencentPretrain checkpoints carry a `target.*` head next to embedding.* / encoder.*: dropped here."""
@@ -276,8 +280,9 @@ class FeatureExtractor(nn.Module):
         multi_headed_attn.py:68); ctx goes to backward_train."""
         if not frames.is_cuda or not ids.is_cuda:
             raise TypeError("lr2ppo_amd: frames / ids must live on the HIP device (no CPU path)")
-        if self.precision != "split_bf16":
-            raise NotImplementedError("forward_train: the encoders train in 'split_bf16' (precision='mxfp8' is inference only)")
+        if self.precision == "mxfp8":
+            raise NotImplementedError("forward_train: the encoders train in 'split_bf16' or 'mxfp8_train' (precision='mxfp8' is "
+                                      "inference only)")
         B, n_img = frames.shape[:2]
         T, L = ids.shape[1:]
         if L != self.seq_length:
@@ -409,6 +414,9 @@ def raw_input_opts(parser):
     parser.add_argument("--fp8_features", action="store_true",
                         help="with --raw_inputs and frozen encoders: every projection of both stacks as an MX-FP8 product on the "
                              "block-scaled MFMA (FeatureExtractor(precision='mxfp8'); a few per cent from the default features)")
+    parser.add_argument("--fp8_finetune", action="store_true",
+                        help="with --raw_inputs --finetune_encoders: train both stacks with MX-FP8 products forward and backward "
+                             "(FeatureExtractor(precision='mxfp8_train'))")
     return parser
 
 
@@ -420,8 +428,12 @@ def build_extractor(args, num_tasks: int = 1, trainable: bool = False) -> Featur
     fp8 = bool(getattr(args, "fp8_features", False))
     if fp8 and trainable:
         raise ValueError("--fp8_features is for frozen feature extraction; drop it or --finetune_encoders")
+    fp8_train = bool(getattr(args, "fp8_finetune", False))
+    if fp8_train and not trainable:
+        raise ValueError("--fp8_finetune trains the encoders in MX-FP8: it needs --finetune_encoders")
+    precision = "mxfp8" if fp8 else ("mxfp8_train" if fp8_train else "split_bf16")
     fx = FeatureExtractor(encoder_args(IMAGE_TOWERS.get(tower, tower), **over), encoder_args(TEXT_CONFIG, **over),
-                          seq_length=args.seq_length, feat_dim=args.visual_feat_dim, precision="mxfp8" if fp8 else "split_bf16")
+                          seq_length=args.seq_length, feat_dim=args.visual_feat_dim, precision=precision)
     text_path, vit_path = getattr(args, "pretrained_model_path", None), getattr(args, "vit_pretrained_model_path", None)
     if text_path or vit_path:
         if not (text_path and vit_path):

@@ -785,6 +785,101 @@ def gemm_mxfp8(a: Mx8, b: Mx8, out: Optional[torch.Tensor], *, bias=None, resid=
     return out if out is not None else (out_mx if out_mx is not None else out_planes)
 
 
+def quant_mxfp8_t(x, *, rows_out: Optional[Mx8] = None, row_blocked: bool = False, colsum: Optional[torch.Tensor] = None,
+                  accumulate: bool = False, act: int = 0, z: Optional[torch.Tensor] = None, dst: Optional[Mx8] = None,
+                  partials: Optional[torch.Tensor] = None, transposed: bool = True):
+    """x [rows, cols] -- fp32 (rows may be strided) or Planes -- through the prologue `act` (0: x; 1: GELU(x); 2: x * GELU'(z)) ->
+    (Mx8 of x^T [cols, rows_pad] (MX blocks down the columns of x; rows_pad = rows rounded up to 128, padding zeros),
+     the row-blocked Mx8 [rows, cols] (rows_out, or a new one with row_blocked=True; byte-identical to quant_mxfp8), else None,
+     colsum: fp32 [cols] column sums written (accumulate: added), else None) -- lr2_quant_mxfp8_t.  partials: workspace of
+    rows_pad / 128 * cols floats for the column sums (allocated when not given).  transposed=False: no x^T (first item None; a
+    forward that keeps nothing for a backward), rows_out / row_blocked then required."""
+    pl = isinstance(x, Planes)
+    if pl:
+        R, K, ld = x.rows, x.cols, x.cols
+    else:
+        _chk_f32(x)
+        if x.dim() != 2 or x.stride(1) != 1:
+            raise ValueError("quant_mxfp8_t: a 2-D fp32 matrix with contiguous rows, or Planes")
+        R, K = x.shape
+        ld = x.stride(0)
+    if K % 64:
+        raise ValueError("quant_mxfp8_t: cols % 64 == 0")
+    if act == 2:
+        _chk_f32(z)
+        if z is None or z.dim() != 2 or tuple(z.shape) != (R, K) or z.stride(1) != 1:
+            raise ValueError("quant_mxfp8_t: act 2 needs z [rows, cols] with contiguous rows")
+    Rp = -(-R // 128) * 128
+    dev = x.buf.device if pl else x.device
+    if transposed:
+        dst = dst or Mx8.empty(K, Rp, dev)
+        if dst.rows != K or dst.cols != Rp:
+            raise ValueError("quant_mxfp8_t: destination must be [cols, rows_pad]")
+    elif dst is not None or (rows_out is None and not row_blocked):
+        raise ValueError("quant_mxfp8_t(transposed=False): no dst, and a row-blocked output")
+    if rows_out is None and row_blocked:
+        rows_out = Mx8.empty(R, K, dev)
+    if rows_out is not None and (rows_out.rows != R or rows_out.cols != K):
+        raise ValueError("quant_mxfp8_t: rows_out must be [rows, cols]")
+    if colsum is not None:
+        _chk_f32(colsum, partials)
+        if colsum.numel() != K:
+            raise ValueError("quant_mxfp8_t: colsum [cols]")
+        if partials is None:
+            partials = torch.empty((Rp // 128) * K, device=dev)
+        elif partials.numel() < (Rp // 128) * K:
+            raise ValueError("quant_mxfp8_t: partials workspace too small")
+    out_bytes = (1.04 if transposed else 0.0) + (1.03 if rows_out is not None else 0.0)
+    with _Timed(f"quant_mxfp8_t_R{R}_C{K}", 0.0, float((8 if act == 2 else 4) * R * K + out_bytes * Rp * K)):
+        _nat.check(_nat.lib().lr2_quant_mxfp8_t(x.data_ptr(), 1 if pl else 0, x.lo_off if pl else 0, ld, _ptr(z),
+                                                z.stride(0) if z is not None else 0, act, _ptr(dst.q) if transposed else None,
+                                                _ptr(dst.s) if transposed else None,
+                                                rows_out.q.data_ptr() if rows_out is not None else None,
+                                                rows_out.s.data_ptr() if rows_out is not None else None, _ptr(colsum),
+                                                _ptr(partials) if colsum is not None else None, 1 if accumulate else 0, R, K,
+                                                _stream()), "lr2_quant_mxfp8_t")
+    return dst, rows_out, colsum
+
+
+@functools.lru_cache(maxsize=4096)
+def mxfp8_wgrad_splits(M: int, N: int, K: int) -> int:
+    """K slices of the weight-gradient product C[M, N] over K (padded) tokens: enough that tiles x slices fill the 256 CUs' 512
+    workgroup slots (two 64-KiB-LDS workgroups per CU) once, and every slice keeps >= 4 K steps of 128."""
+    tiles = (M // 128) * (N // 128)
+    return max(1, min(-(-512 // tiles), K // 512))
+
+
+def gemm_mxfp8_wgrad(a_t: Mx8, b_t: Mx8, out: torch.Tensor, *, splits: Optional[int] = None, accumulate: bool = False,
+                     workspace: Optional[torch.Tensor] = None):
+    """out[M, N] (+)= a_t . b_t^T with a_t [M, K], b_t [N, K] blocked along K (quant_mxfp8_t of dY and X: a weight gradient dY^T X),
+    out with contiguous rows (any row stride: a view of a flat gradient buffer).  K-sliced (lr2_gemm_mxfp8_wgrad): workspace holds
+    splits * M * N floats; the slices are summed in a fixed order, so the bits do not depend on timing."""
+    _chk_f32(out, workspace)
+    M, N, K = a_t.rows, b_t.rows, a_t.cols
+    if b_t.cols != K or out.dim() != 2 or tuple(out.shape) != (M, N) or out.stride(1) != 1:
+        raise ValueError("gemm_mxfp8_wgrad: a_t [M, K], b_t [N, K], out [M, N] with contiguous rows")
+    sp = splits or mxfp8_wgrad_splits(M, N, K)
+    sp = max(1, min(sp, K // 128))
+    if sp > 1 and (workspace is None or workspace.numel() < sp * M * N):
+        raise ValueError(f"gemm_mxfp8_wgrad: workspace too small: need {sp * M * N} floats")
+    with _Timed(f"gemm_mxfp8_wgrad_M{M}_N{N}_K{K}", 2.0 * M * N * K, float(M * K + N * K + (8 * sp + 4) * M * N)):
+        _nat.check(_nat.lib().lr2_gemm_mxfp8_wgrad(a_t.q.data_ptr(), a_t.s.data_ptr(), b_t.q.data_ptr(), b_t.s.data_ptr(), out.data_ptr(),
+                                                   out.stride(0), 1 if accumulate else 0, _ptr(workspace) if sp > 1 else None, sp,
+                                                   M, N, K, _stream()), "lr2_gemm_mxfp8_wgrad")
+    return out
+
+
+def dropout_residual(y: torch.Tensor, resid: torch.Tensor, out: torch.Tensor, drop: Drop):
+    """out = resid + dropout_mask(y) / (1 - p) over contiguous fp32 tensors of one shape (lr2_dropout_residual)."""
+    _chk_f32(y, resid, out)
+    if not (y.is_contiguous() and resid.is_contiguous() and out.is_contiguous()) or y.numel() != resid.numel() or y.numel() != out.numel():
+        raise ValueError("dropout_residual: contiguous tensors of one size")
+    with _Timed(f"dropout_residual_{y.numel()}", 0.0, 12.0 * y.numel()):
+        _nat.check(_nat.lib().lr2_dropout_residual(y.data_ptr(), resid.data_ptr(), out.data_ptr(), y.numel(), drop.p, drop.seed, drop.site,
+                                                   _stream()), "lr2_dropout_residual")
+    return out
+
+
 def self_attn_fwd_bf16(qkv: torch.Tensor, seg, *, batch, heads, L, head_dim, scale, out: Optional[torch.Tensor] = None,
                        out_mx: Optional[Mx8] = None):
     """Encoder self-attention of the MX-FP8 mode (lr2_self_attn_fwd_bf16).  qkv: ONE bf16 plane [batch * L, 3E] = [Q | K | V] (a 2-byte

@@ -112,6 +112,10 @@ class _StackPlanes:
 
 
 class TransformerEncoder(nn.Module):
+    # True: the training schedule (and, for bit-identical features, every forward) runs the four projections of every layer as MX-FP8
+    # products, forward and backward (_forward_train_fp8 / _backward_train_fp8; FeatureExtractor(precision="mxfp8_train"))
+    fp8_train = False
+
     def __init__(self, args):
         super().__init__()
         self.mask = args.mask
@@ -152,6 +156,8 @@ class TransformerEncoder(nn.Module):
         needs_grad = torch.is_grad_enabled() and (emb.requires_grad or any(p.requires_grad for p in self.parameters()))
         if needs_grad:
             return _EncoderFn.apply(self, emb, seg, *list(self.parameters()))
+        if self.fp8_train:
+            return self._forward_train_fp8(emb, seg, save=False)[0]      # no backward follows: nothing kept, no x^T written
         if self.training and any(l.dropout_1.p > 0 for l in self.transformer):
             out, _ = self._forward_train(emb, seg)       # dropout without a graph (torch.no_grad() in train mode)
             return out
@@ -163,7 +169,7 @@ class TransformerEncoder(nn.Module):
         its keys and values for every row but its query, output projection and feed-forward for row 0 only: 5/6 of that
         layer's matrix work is never consumed and is not computed.  With gradients enabled: the full forward, sliced."""
         needs_grad = torch.is_grad_enabled() and (emb.requires_grad or any(p.requires_grad for p in self.parameters()))
-        if needs_grad or (self.training and any(l.dropout_1.p > 0 for l in self.transformer)):
+        if needs_grad or self.fp8_train or (self.training and any(l.dropout_1.p > 0 for l in self.transformer)):
             return self.forward(emb, seg)[:, 0, :]
         if emb.dtype != torch.float32 or not emb.is_cuda:
             raise TypeError("lr2ppo_amd: emb must be a float32 tensor on the HIP device (no CPU path)")
@@ -350,6 +356,8 @@ class TransformerEncoder(nn.Module):
 
     @torch.no_grad()
     def _forward_train(self, emb, seg):
+        if self.fp8_train:
+            return self._forward_train_fp8(emb, seg)
         B, L, E, H, hd, M, F = self._dims(emb)
         dev = emb.device
         if self._ws is None or self._ws.device != dev:
@@ -459,6 +467,8 @@ class TransformerEncoder(nn.Module):
     def _backward_train(self, saved, dout, G=None):
         """-> (d emb [B, L, E], {parameter: gradient}) for the forward that produced `saved`.  G: write the parameter gradients
         into these tensors (grad_buffers()) instead of a fresh allocation."""
+        if saved.get("fp8"):
+            return self._backward_train_fp8(saved, dout, G)
         B, L, E, H, hd, M, F = saved["dims"]
         dev, seg, W = dout.device, saved["seg"], saved["W"]
         ws = self._ws
@@ -544,6 +554,230 @@ class TransformerEncoder(nn.Module):
                 engine.linear_dgrad(ws, dqkv_p, w["wqkv"], dprev, M, E, 3 * E, resid=d_t1, w_f32=w["wqkv_f32"] if big_dqkv else None)
             dh = dprev
             saved["layers"][i] = None                                   # release this layer's activations
+        return dh.view(B, L, E), G
+
+
+    # ---- MX-FP8 training schedule (FeatureExtractor(precision="mxfp8_train")) ------------------------------------------------------
+    # _forward_train / _backward_train in the same order, with the same dropout sites, `saved` / G contract and gradient layout, but
+    # every projection -- forward, input gradient, weight gradient -- an MX-FP8 product (csrc/fp8.hip, csrc/fp8_train.hip).  The
+    # attention (3-pass planes kernels), every LayerNorm, the residual stream and the embeddings stay as they are.
+    def _fp8_train_weights(self):
+        """Per layer: the four projection weights quantised once per parameter write -- row-blocked (forward: B = W [out, in]) and
+        column-blocked (input gradient: B = W^T [in, out], MX blocks along `out`)."""
+        sig = tuple((p.data_ptr(), p._version, ops.param_write_count(p)) for p in self.parameters())
+        if getattr(self, "_fp8t_sig", None) != sig:
+            out = []
+            for layer in self.transformer:
+                att, ffn = layer.self_attn, layer.feed_forward
+                ent = {"bqkv": torch.cat([l.bias.data for l in att.linear_layers], 0)}
+                for k, w in (("wqkv", torch.cat([l.weight.data for l in att.linear_layers], 0)), ("wo", att.final_linear.weight.data),
+                             ("w1", ffn.linear_1.weight.data), ("w2", ffn.linear_2.weight.data)):
+                    ent[k + "_t"], ent[k], _ = ops.quant_mxfp8_t(w.contiguous(), row_blocked=True)
+                out.append(ent)
+            self._fp8t_w, self._fp8t_sig = out, sig
+            self.fp8_weight_quantisations = getattr(self, "fp8_weight_quantisations", 0) + 1
+        return self._fp8t_w
+
+    def _mx(self, name, rows, cols, dev):
+        """A named reusable Mx8 scratch matrix (operands consumed inside one forward or backward call)."""
+        bufs = self.__dict__.setdefault("_mx_bufs", {})
+        m = bufs.get(name)
+        if m is None or m.rows != rows or m.cols != cols or m.q.device != dev:
+            m = bufs[name] = ops.Mx8.empty(rows, cols, dev)
+        return m
+
+    @torch.no_grad()
+    def _forward_train_fp8(self, emb, seg, save: bool = True):
+        """save=False (a forward no backward follows: extract(), eval and rollout forwards): the same arithmetic and the same output
+        bits, but the activations live in reused workspace buffers and the column-blocked copies are not written."""
+        B, L, E, H, hd, M, F = self._dims(emb)
+        if E % 128 or F % 128:
+            raise ValueError("mxfp8_train: hidden and feed-forward widths must be multiples of 128")
+        dev = emb.device
+        if self._ws is None or self._ws.device != dev:
+            self._ws = engine.Workspace(dev)
+        ws = self._ws
+        seg = seg.to(device=dev, dtype=torch.int64).contiguous().view(-1)
+        W = self._fp8_train_weights()
+        p = float(self.transformer[0].dropout_1.p) if self.training else 0.0
+        seed = runtime.next_drop(p, 0).seed if p > 0 else 0
+        drop = (lambda site: ops.Drop(p, seed, site)) if p > 0 else (lambda site: None)
+        pre = self.layernorm_positioning == "pre"
+        scale = 1.0 / math.sqrt(float(hd))
+        xs, ys = ws.mat("fp8t_x", M, E), ws.mat("fp8t_y", M, E)        # transient fp32: LayerNorm output, projection before dropout
+        x_q, f_q = self._mx("fx", M, E, dev), self._mx("ff", M, F, dev)  # transient row-blocked A operands
+        # what the backward reads: fresh tensors when saving, else named workspace buffers (the layer output alternates between two)
+        mat = (lambda name, r, c: torch.empty(r, c, device=dev)) if save else (lambda name, r, c: ws.mat("fp8e:" + name, r, c))
+        vec = (lambda name, n: torch.empty(n, device=dev)) if save else (lambda name, n: ws.vec("fp8e:" + name, n))
+        pl = (lambda name, r, c: ops.Planes.empty(r, c, dev)) if save else (lambda name, r, c: ws.planes("fp8e:" + name, r, c))
+
+        def quant(x, a_q, act=0):
+            """row-blocked a_q of x (GELU(x) with act 1), and, when saving, the column-blocked copy of x^T the weight gradient reads"""
+            return ops.quant_mxfp8_t(x, rows_out=a_q, act=act, transposed=save)[0]
+
+        def proj_out(a_q, wq, bias, resid, out, site):
+            """out = resid + dropout(a . W^T + bias): the split-bf16 epilogue's order"""
+            if site is None:
+                ops.gemm_mxfp8(a_q, wq, out, bias=bias, resid=resid)
+            else:
+                ops.gemm_mxfp8(a_q, wq, ys, bias=bias)
+                ops.dropout_residual(ys, resid, out, site)
+
+        h = emb.detach().contiguous().view(M, E)
+        saved = {"fp8": True, "layers": [], "seg": seg, "dims": (B, L, E, H, hd, M, F), "drop": (p, seed), "W": W}
+        for i, (layer, w) in enumerate(zip(self.transformer, W)):
+            att, ffn = layer.self_attn, layer.feed_forward
+            ln1, ln2 = layer.layer_norm_1, layer.layer_norm_2
+            s0 = 4 * i
+            S = {}
+            if pre:
+                S["m1"], S["r1"], S["h_in"] = vec("m1", M), vec("r1", M), h
+                ops.layernorm_fwd(h, ln1.gamma.data, ln1.beta.data, xs, S["m1"], S["r1"], rows=M, D=E, eps=ln1.eps, mode=1)
+                S["xT"] = quant(xs, x_q)
+            else:
+                S["xT"] = quant(h, x_q)
+            qkv_p, o_p = pl("qkv", M, 3 * E), pl("o", M, E)
+            ops.gemm_mxfp8(x_q, w["wqkv"], None, bias=w["bqkv"], out_planes=qkv_p)
+            S["lse"] = vec("lse", B * H * L)
+            ops.self_attn_fwd(qkv_p, seg, o_p, batch=B, heads=H, L=L, head_dim=hd, scale=scale, lse=S["lse"], drop=drop(s0))
+            S["oT"] = quant(o_p, x_q)
+            t1 = mat("t1", M, E)
+            proj_out(x_q, w["wo"], att.final_linear.bias.data, h, t1, drop(s0 + 1))
+            z = mat("z", M, F)
+            S.update(qkv_p=qkv_p, o_p=o_p, t1=t1, z=z)
+            hn = mat("h%d" % (i & 1), M, E)
+            if pre:
+                S["m2"], S["r2"] = vec("m2", M), vec("r2", M)
+                ops.layernorm_fwd(t1, ln2.gamma.data, ln2.beta.data, xs, S["m2"], S["r2"], rows=M, D=E, eps=ln2.eps, mode=1)
+                S["x2T"] = quant(xs, x_q)
+                ops.gemm_mxfp8(x_q, w["w1"], z, bias=ffn.linear_1.bias.data)
+                S["ffT"] = quant(z, f_q, act=1)
+                proj_out(f_q, w["w2"], ffn.linear_2.bias.data, t1, hn, drop(s0 + 2))
+            else:
+                inter, S["m1"], S["r1"] = mat("inter", M, E), vec("m1", M), vec("r1", M)
+                ops.layernorm_fwd(t1, ln1.gamma.data, ln1.beta.data, inter, S["m1"], S["r1"], rows=M, D=E, eps=ln1.eps, mode=1)
+                S["x2T"] = quant(inter, x_q)
+                ops.gemm_mxfp8(x_q, w["w1"], z, bias=ffn.linear_1.bias.data)
+                S["ffT"] = quant(z, f_q, act=1)
+                t2 = mat("t2", M, E)
+                proj_out(f_q, w["w2"], ffn.linear_2.bias.data, inter, t2, drop(s0 + 2))
+                S["m2"], S["r2"] = vec("m2", M), vec("r2", M)
+                ops.layernorm_fwd(t2, ln2.gamma.data, ln2.beta.data, hn, S["m2"], S["r2"], rows=M, D=E, eps=ln2.eps, mode=1)
+                S["t2"] = t2
+            h = hn
+            if save:
+                saved["layers"].append(S)
+        if self.final_layernorm:
+            out = torch.empty(B, L, E, device=dev)
+            mf, rf = vec("mf", M), vec("rf", M)
+            ops.layernorm_fwd(h, self.layer_norm.gamma.data, self.layer_norm.beta.data, out.view(M, E), mf, rf,
+                              rows=M, D=E, eps=self.layer_norm.eps, mode=1)
+            saved["h_final"], saved["mf"], saved["rf"] = h, mf, rf
+        else:
+            out = h.view(B, L, E) if save else h.clone().view(B, L, E)      # not a view of a reused workspace buffer
+        return out, (saved if save else None)
+
+    @torch.no_grad()
+    def _backward_train_fp8(self, saved, dout, G=None):
+        """_backward_train for a forward of _forward_train_fp8: every product's operands quantised once along the axis it reduces
+        over (quant_mxfp8_t: one read of a gradient gives the input-gradient product's A, the weight-gradient product's A^T and the
+        bias gradient), weight gradients written straight into G's views by the K-sliced product."""
+        B, L, E, H, hd, M, F = saved["dims"]
+        dev, seg, W = dout.device, saved["seg"], saved["W"]
+        ws = self._ws
+        p, seed = saved["drop"]
+        drop = (lambda site: ops.Drop(p, seed, site)) if p > 0 else (lambda site: None)
+        mat = lambda name, r, c: ws.mat("bwd:" + name, r, c)            # noqa: E731
+        pl = lambda name, r, c: ws.planes("bwd:" + name, r, c)          # noqa: E731
+        if G is None:
+            G, qkv_blocks = self._grad_layout(torch.empty(sum(q.numel() for q in self.parameters()), device=dev))
+        else:
+            if G is not getattr(self, "_gviews", None):
+                raise ValueError("_backward_train(G=...): pass grad_buffers()")
+            qkv_blocks = self._gqkv
+        partials = ws.vec("ln_partials", ops.LN_BWD_BLOCKS * 2 * E)
+        dsum_ws = ws.vec("attn_dsum", B * H * L)
+        Mp = -(-M // 128) * 128
+        cs_ws = ws.vec("fp8t_colsum", (Mp // 128) * 3 * E if 3 * E > F else (Mp // 128) * F)
+        pre = self.layernorm_positioning == "pre"
+        scale = 1.0 / math.sqrt(float(hd))
+        d_q, dT = self._mx("bd", M, max(3 * E, F), dev), self._mx("bdT", max(3 * E, F), Mp, dev)
+
+        def quant_grad(x, cols, bias_grad, act=0, z=None):
+            """row-blocked [M, cols] + column-blocked [cols, Mp] of a gradient, and its column sums into bias_grad"""
+            a = ops.Mx8(d_q.q, d_q.s, M, cols)
+            at = ops.Mx8(dT.q, dT.s, cols, Mp)
+            ops.quant_mxfp8_t(x, rows_out=a, dst=at, colsum=bias_grad, partials=cs_ws, act=act, z=z)
+            return a, at
+
+        def wgrad(at, bt, out):
+            M_, N_ = at.rows, bt.rows
+            sp = ops.mxfp8_wgrad_splits(M_, N_, Mp)
+            ops.gemm_mxfp8_wgrad(at, bt, out, splits=sp, workspace=ws.vec("fp8t_wgrad", sp * M_ * N_) if sp > 1 else None)
+
+        dh = dout.contiguous().view(M, E)
+        if self.final_layernorm:
+            ln = self.layer_norm
+            dnew = mat("dh0", M, E)
+            top = self.layers_num - 1
+            ops.layernorm_bwd(dh, saved["h_final"], ln.gamma.data, saved["mf"], saved["rf"], dnew, partials, G[ln.gamma],
+                              G[ln.beta], rows=M, D=E, mode=1, eps=ln.eps, dx_planes=pl("dff_p", M, E) if pre else None,
+                              drop=drop(4 * top + 2) if pre else None)
+            dh = dnew
+        dff_ready = pre and self.final_layernorm
+        flip = 1
+        for i in reversed(range(self.layers_num)):
+            layer, w, S = self.transformer[i], W[i], saved["layers"][i]
+            att, ffn = layer.self_attn, layer.feed_forward
+            ln1, ln2 = layer.layer_norm_1, layer.layer_norm_2
+            s0 = 4 * i
+            dff_p = pl("dff_p", M, E)
+            if pre:
+                if not dff_ready:
+                    ops.dropout_planes(dh, dff_p, drop(s0 + 2))
+            else:
+                d_t2 = mat("d_t2", M, E)
+                ops.layernorm_bwd(dh, S["t2"], ln2.gamma.data, S["m2"], S["r2"], d_t2, partials, G[ln2.gamma], G[ln2.beta],
+                                  rows=M, D=E, dx_planes=dff_p, drop=drop(s0 + 2), mode=1, eps=ln2.eps)
+            # FFN-2: dW2 = dff^T . GELU(z), dh_ff = dff . W2; FFN-1: dz = dh_ff * GELU'(z), dW1 = dz^T . x2, d x2 = dz . W1
+            a, at = quant_grad(dff_p, E, G[ffn.linear_2.bias])
+            wgrad(at, S["ffT"], G[ffn.linear_2.weight])
+            dff32 = mat("dff32", M, F)
+            ops.gemm_mxfp8(a, w["w2_t"], dff32)
+            a, at = quant_grad(dff32, F, G[ffn.linear_1.bias], act=2, z=S["z"])
+            wgrad(at, S["x2T"], G[ffn.linear_1.weight])
+            d_t1, dao_p, d_x2 = mat("d_t1", M, E), pl("dao_p", M, E), mat("d_x2", M, E)
+            if pre:
+                ops.gemm_mxfp8(a, w["w1_t"], d_x2)
+                ops.layernorm_bwd(d_x2, S["t1"], ln2.gamma.data, S["m2"], S["r2"], d_t1, partials, G[ln2.gamma], G[ln2.beta],
+                                  rows=M, D=E, resid_grad=dh, dx_planes=dao_p, drop=drop(s0 + 1), mode=1, eps=ln2.eps)
+            else:
+                ops.gemm_mxfp8(a, w["w1_t"], d_x2, resid=d_t2)
+                ops.layernorm_bwd(d_x2, S["t1"], ln1.gamma.data, S["m1"], S["r1"], d_t1, partials, G[ln1.gamma], G[ln1.beta],
+                                  rows=M, D=E, dx_planes=dao_p, drop=drop(s0 + 1), mode=1, eps=ln1.eps)
+            # output projection, attention, QKV
+            a, at = quant_grad(dao_p, E, G[att.final_linear.bias])
+            wgrad(at, S["oT"], G[att.final_linear.weight])
+            do_p, dqkv_p = pl("do_p", M, E), pl("dqkv_p", M, 3 * E)
+            ops.gemm_mxfp8(a, w["wo_t"], None, out_planes=do_p)
+            ops.self_attn_bwd(S["qkv_p"], do_p, seg, dqkv_p, S["lse"], dsum_ws, batch=B, heads=H, L=L, head_dim=hd, scale=scale,
+                              drop=drop(s0), o=S["o_p"])
+            a, at = quant_grad(dqkv_p, 3 * E, qkv_blocks[i][1])
+            wgrad(at, S["xT"], qkv_blocks[i][0])
+            dprev = torch.empty(M, E, device=dev) if i == 0 else mat("dh%d" % flip, M, E)
+            flip ^= 1
+            if pre:
+                d_x1 = mat("d_x1", M, E)
+                ops.gemm_mxfp8(a, w["wqkv_t"], d_x1)
+                nxt = i > 0
+                ops.layernorm_bwd(d_x1, S["h_in"], ln1.gamma.data, S["m1"], S["r1"], dprev, partials, G[ln1.gamma], G[ln1.beta],
+                                  rows=M, D=E, resid_grad=d_t1, mode=1, eps=ln1.eps, dx_planes=dff_p if nxt else None,
+                                  drop=drop(s0 - 4 + 2) if nxt else None)
+                dff_ready = nxt
+            else:
+                ops.gemm_mxfp8(a, w["wqkv_t"], dprev, resid=d_t1)
+            dh = dprev
+            saved["layers"][i] = None
         return dh.view(B, L, E), G
 
 

@@ -82,12 +82,15 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--passes", type=int, default=3)
     ap.add_argument("--detail", action="store_true", help="per-signature launch averages")
-    ap.add_argument("--train", action="store_true", help="time forward + backward (train mode, dropout 0.1) instead")
+    ap.add_argument("--train", action="store_true", help="time forward + backward (train mode, dropout 0.1) instead; with "
+                    "--ppo-shapes: both towers at the PPO sizes (ViT over batch*16 frames, RoBERTa over batch*2 sequences)")
+    ap.add_argument("--precision", choices=("split_bf16", "mxfp8_train"), default="split_bf16",
+                    help="--train: the encoders' training precision (TransformerEncoder.fp8_train)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     ops.set_gemm_passes(a.passes)
     torch.manual_seed(0)
-    if a.ppo_shapes:
+    if a.ppo_shapes and not a.train:
         print(measure_forward(a.batch, iters=a.iters, passes=a.passes, dev=dev))
         return
     total_ms, total_fl = 0.0, 0.0
@@ -99,9 +102,11 @@ def main():
                     p.normal_(0, 0.02)
         enc = enc.to(dev)
         enc = enc.train() if a.train else enc.eval()
-        emb = torch.randn(a.batch, L, 768, device=dev, requires_grad=a.train)
-        seg = torch.ones(a.batch, L, dtype=torch.int64, device=dev)
-        dout = torch.randn(a.batch, L, 768, device=dev)
+        enc.fp8_train = a.train and a.precision == "mxfp8_train"
+        B = (a.batch * 16 if name.startswith("vit") else a.batch * 2) if a.ppo_shapes else a.batch
+        emb = torch.randn(B, L, 768, device=dev, requires_grad=a.train)
+        seg = torch.ones(B, L, dtype=torch.int64, device=dev)
+        dout = torch.randn(B, L, 768, device=dev)
 
         def run():
             if a.train:
@@ -119,7 +124,7 @@ def main():
         e.record()
         torch.cuda.synchronize()
         ms = s.elapsed_time(e) / a.iters
-        fl = flops(a.batch, L) * (3.0 if a.train else 1.0)
+        fl = flops(B, L) * (3.0 if a.train else 1.0)
         total_ms += ms
         total_fl += fl
         ops.profile_start()
@@ -129,7 +134,7 @@ def main():
         for k, v in prof.items():
             c = k.split("_")[0] + ("_" + k.split("_")[1] if k.startswith("gemm") else "")
             classes[c] = classes.get(c, 0.0) + v["ms"]
-        print(f"{name:13s} B={a.batch} L={L}: {ms:7.3f} ms/forward  {fl / ms / 1e9:7.1f} TFLOP/s (algorithmic)  "
+        print(f"{name:13s} B={B} L={L} {a.precision if a.train else ''}: {ms:7.3f} ms/{'step' if a.train else 'forward'}  {fl / ms / 1e9:7.1f} TFLOP/s (algorithmic)  "
               f"frac of 2.5 PF bf16 dense x{a.passes} passes: {a.passes * fl / ms / 1e9 / 2500:.3f}", flush=True)
         print("    events:", {k: round(v, 3) for k, v in sorted(classes.items(), key=lambda kv: -kv[1])}, flush=True)
         if a.detail:
