@@ -155,13 +155,16 @@ class FeatureExtractor(nn.Module):
     precision: "split_bf16" (default: the fp32-grade parity path) or "mxfp8" -- extract() / no-grad forward() run every
     projection of both stacks as an MX-FP8 product (TransformerEncoder.forward_fp8); training paths refuse that mode -- or
     "mxfp8_train": fine-tuning in MX-FP8, every projection's forward, input gradient and weight gradient an MX-FP8 product
-    (TransformerEncoder._forward_train_fp8 / _backward_train_fp8) on every route, extract() included (that forward, dropout off)."""
+    (TransformerEncoder._forward_train_fp8 / _backward_train_fp8) on every route, extract() included (that forward, dropout off).
+    recompute: the training forwards of both towers keep each layer's input only and the backward re-runs a layer's forward right
+    before that layer's backward (TransformerEncoder.recompute): the same bits, ~1/12 of the activation memory, one more
+    forward per step.  Embeddings, the projection and the heads keep their activations."""
 
     PRECISIONS = ("split_bf16", "mxfp8", "mxfp8_train")
 
     def __init__(self, vit_args: Optional[argparse.Namespace] = None, text_args: Optional[argparse.Namespace] = None,
                  vocab_size: int = ROBERTA_VOCAB, seq_length: int = 196, feat_dim: Optional[int] = None,
-                 precision: str = "split_bf16"):
+                 precision: str = "split_bf16", recompute: bool = False):
         super().__init__()
         self.vit_args = vit_args or encoder_args(VIT_CONFIG)
         self.text_args = text_args or encoder_args(TEXT_CONFIG)
@@ -172,13 +175,24 @@ class FeatureExtractor(nn.Module):
                              f"heads' feature width {self.feat_dim}, got {self.text_args.hidden_size}")
         if precision not in self.PRECISIONS:
             raise ValueError(f"precision must be one of {self.PRECISIONS}")
-        self.precision = precision
+        if recompute and precision == "mxfp8":
+            raise ValueError("recompute trades time for memory in the TRAINING schedules; precision='mxfp8' is inference only")
+        self.precision, self.recompute = precision, bool(recompute)
         self.image = EncoderStack(self.vit_args, vocab_size)
         self.text = EncoderStack(self.text_args, vocab_size)
         self.visual_projection = (VisualProjection(self.vit_args.hidden_size, self.feat_dim)
                                   if self.vit_args.hidden_size != self.feat_dim else None)
         self.text.embedding.defer_id_check = True          # one check per extract() at its end, not one sync per call
         self.image.encoder.fp8_train = self.text.encoder.fp8_train = precision == "mxfp8_train"
+        self.image.encoder.recompute = self.text.encoder.recompute = self.recompute
+
+    def saved_activation_bytes(self, frames_shape, ids_shape) -> int:
+        """Bytes of encoder activations forward_train keeps until backward_train for frames [B, n_img, ...] and ids [B, T, L]: the
+        sum over the two towers (TransformerEncoder.saved_activation_bytes).  Arithmetic only."""
+        B, n_img = frames_shape[:2]
+        _, T, L = ids_shape
+        return (self.image.encoder.saved_activation_bytes(B * n_img, self.vit_args.max_seq_length)
+                + self.text.encoder.saved_activation_bytes(B * T, L))
 
     def load_pretrained(self, vit_path: Optional[str] = None, text_path: Optional[str] = None):
         """Released TencentPretrain checkpoints carry a `target.*` head next to embedding.* / encoder.*: dropped here."""
@@ -417,6 +431,9 @@ def raw_input_opts(parser):
     parser.add_argument("--fp8_finetune", action="store_true",
                         help="with --raw_inputs --finetune_encoders: train both stacks with MX-FP8 products forward and backward "
                              "(FeatureExtractor(precision='mxfp8_train'))")
+    parser.add_argument("--recompute_activations", action="store_true",
+                        help="with --finetune_encoders: keep one layer's activations at a time (each layer's forward runs again "
+                             "in front of its backward: same gradients, ~1/12 of the activation memory, one more forward per step)")
     return parser
 
 
@@ -431,9 +448,13 @@ def build_extractor(args, num_tasks: int = 1, trainable: bool = False) -> Featur
     fp8_train = bool(getattr(args, "fp8_finetune", False))
     if fp8_train and not trainable:
         raise ValueError("--fp8_finetune trains the encoders in MX-FP8: it needs --finetune_encoders")
+    recompute = bool(getattr(args, "recompute_activations", False))
+    if recompute and not trainable:
+        raise ValueError("--recompute_activations is a training-memory switch: it needs --finetune_encoders")
     precision = "mxfp8" if fp8 else ("mxfp8_train" if fp8_train else "split_bf16")
     fx = FeatureExtractor(encoder_args(IMAGE_TOWERS.get(tower, tower), **over), encoder_args(TEXT_CONFIG, **over),
-                          seq_length=args.seq_length, feat_dim=args.visual_feat_dim, precision=precision)
+                          seq_length=args.seq_length, feat_dim=args.visual_feat_dim, precision=precision,
+                          recompute=recompute)
     text_path, vit_path = getattr(args, "pretrained_model_path", None), getattr(args, "vit_pretrained_model_path", None)
     if text_path or vit_path:
         if not (text_path and vit_path):

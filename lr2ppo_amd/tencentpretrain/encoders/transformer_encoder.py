@@ -111,10 +111,56 @@ class _StackPlanes:
         self.sig = self.signature(enc)
 
 
+class _Kept:
+    """Where a training layer's tensors go when the backward reads them from the forward: carved from one Arena (split-bf16; the
+    names are unused, the order of the calls is the layout), or a fresh tensor each (no arena: MX-FP8)."""
+
+    def __init__(self, dev, arena=None):
+        self.dev, self.arena = dev, arena
+
+    def mat(self, name, rows, cols):
+        return self.arena.mat(rows, cols) if self.arena is not None else torch.empty(rows, cols, device=self.dev)
+
+    def vec(self, name, numel):
+        return self.arena.vec(numel) if self.arena is not None else torch.empty(numel, device=self.dev)
+
+    def planes(self, name, rows, cols):
+        return self.arena.planes(rows, cols) if self.arena is not None else ops.Planes.empty(rows, cols, self.dev)
+
+    def mx_t(self, name, rows, cols):
+        return None                                                      # quant_mxfp8_t allocates the column-blocked copy
+
+
+class _Reused:
+    """The same tensors as named workspace buffers, reused by every layer and every step: a forward nothing reads afterwards, or a
+    layer recomputed right in front of its backward.  out: the _Kept that holds the layer output (`hn*`) instead -- the recomputing
+    forward keeps it as the next layer's input."""
+
+    def __init__(self, enc, dev, prefix, out=None):
+        self.enc, self.dev, self.prefix, self.out = enc, dev, prefix, out
+
+    def mat(self, name, rows, cols):
+        if self.out is not None and name.startswith("hn"):
+            return self.out.mat(name, rows, cols)
+        return self.enc._ws.mat(self.prefix + name, rows, cols)
+
+    def vec(self, name, numel):
+        return self.enc._ws.vec(self.prefix + name, numel)
+
+    def planes(self, name, rows, cols):
+        return self.enc._ws.planes(self.prefix + name, rows, cols)
+
+    def mx_t(self, name, rows, cols):
+        return self.enc._mx(self.prefix + name, rows, cols, self.dev)
+
+
 class TransformerEncoder(nn.Module):
     # True: the training schedule (and, for bit-identical features, every forward) runs the four projections of every layer as MX-FP8
     # products, forward and backward (_forward_train_fp8 / _backward_train_fp8; FeatureExtractor(precision="mxfp8_train"))
     fp8_train = False
+    # True: the training forward keeps each layer's INPUT only; the backward re-runs layer i's forward (same dropout seed and sites, same
+    # weight operands: the same bits) into reused workspace buffers right before layer i's backward (DESIGN 4.4)
+    recompute = False
 
     def __init__(self, args):
         super().__init__()
@@ -354,76 +400,111 @@ class TransformerEncoder(nn.Module):
         B, L, E = emb.shape
         return B, L, E, self.heads_num, E // self.heads_num, B * L, self.transformer[0].feed_forward.linear_1.out_features
 
+    def _saved_bytes(self, B, L, recompute):
+        """(bytes per layer, bytes behind the last layer) a training forward keeps until its backward.  split-bf16: the sizes the
+        activation arena is allocated with.  MX-FP8 keeps separate tensors: their sum."""
+        E, H, F = self.hidden_size, self.heads_num, self.transformer[0].feed_forward.linear_1.out_features
+        M = B * L
+        pre = self.layernorm_positioning == "pre"
+        if recompute:                                                   # each layer's output = the next one's input (256: alignment)
+            return 4 * M * E + 256, (8 * M + 8 * 256 if self.final_layernorm else 0)
+        if self.fp8_train:
+            Mp = -(-M // 128) * 128                                     # x^T, o^T, x2^T [E, Mp] and GELU(z)^T [F, Mp]: bytes + scale bytes
+            return ((24 if pre else 32) * M * E + 4 * M * F + 16 * M + 4 * B * H * L + (3 * E + F) * (Mp + Mp // 32),
+                    8 * M if self.final_layernorm else 0)
+        # per layer 32 (pre-LN) / 40 (post-LN) x M x E bytes of hidden-width tensors, 8 x M x F of feed-forward ones, 4 row
+        # statistics; + the final LayerNorm's statistics
+        return (32 if pre else 40) * M * E + 8 * M * F + 16 * M + 4 * B * H * L + 20 * 256, 4 * M * E + 8 * M + 8 * 256
+
+    def saved_activation_bytes(self, batch: int, seq_len: int, recompute=None) -> int:
+        """Bytes of activations one training forward over [batch, seq_len] keeps between forward and backward (the arena of
+        _forward_train; recompute=None: this encoder's own setting).  Arithmetic only: callable on a CPU module."""
+        per_layer, tail = self._saved_bytes(batch, seq_len, self.recompute if recompute is None else bool(recompute))
+        return self.layers_num * per_layer + tail
+
+    def _layer_fwd_train(self, i, w, h, h_p, A, seg, dims, drop):
+        """Layer i of the split-bf16 training schedule.  h: the layer's input [M, E] (fp32); h_p: its planes (post-LN; None for pre-LN);
+        A: the allocator of everything the layer writes (_Kept: the forward's arena; _Reused: workspace buffers).
+        -> (S: what the layer's backward reads, the layer's output, its planes (post-LN) or None)."""
+        B, L, E, H, hd, M, F = dims
+        ws = self._ws                                                   # split-K / reduction scratch only
+        layer = self.transformer[i]
+        att, ffn = layer.self_attn, layer.feed_forward
+        ln1, ln2 = layer.layer_norm_1, layer.layer_norm_2
+        pre = self.layernorm_positioning == "pre"
+        scale = 1.0 / math.sqrt(float(hd))
+        big_qkv, big_ff = ops.use_gemm256(M, 3 * E, E), ops.use_gemm256(M, F, E)
+        mat, vec, pl = A.mat, A.vec, A.planes
+        s0 = 4 * i
+        S = {}
+        if pre:
+            x_p, S["m1"], S["r1"], S["h_in"] = pl("x_p", M, E), vec("m1", M), vec("r1", M), h
+            ops.layernorm_fwd(h, ln1.gamma.data, ln1.beta.data, None, S["m1"], S["r1"], rows=M, D=E, eps=ln1.eps, mode=1,
+                              out_planes=x_p)
+        else:
+            x_p = h_p
+        qkv_p, o_p, t1 = pl("qkv_p", M, 3 * E), pl("o_p", M, E), mat("t1", M, E)
+        engine.linear_fwd(ws, x_p, w["wqkv" if big_qkv else "wqkv_t"], w["bqkv"], None, M, 3 * E, E, out_planes=qkv_p)
+        S["lse"] = vec("lse", B * H * L)                                # the attention's log-sum-exp: an input of its backward
+        ops.self_attn_fwd(qkv_p, seg, o_p, batch=B, heads=H, L=L, head_dim=hd, scale=scale, lse=S["lse"], drop=drop(s0))
+        engine.linear_fwd(ws, o_p, w["wo"], att.final_linear.bias.data, t1, M, E, E, resid=h, drop=drop(s0 + 1))
+        z, ff_p = mat("z", M, F), pl("ff_p", M, F)
+        S.update(x_p=x_p, qkv_p=qkv_p, o_p=o_p, t1=t1, z=z, ff_p=ff_p)
+        if pre:
+            x2_p, S["m2"], S["r2"] = pl("x2_p", M, E), vec("m2", M), vec("r2", M)
+            ops.layernorm_fwd(t1, ln2.gamma.data, ln2.beta.data, None, S["m2"], S["r2"], rows=M, D=E, eps=ln2.eps, mode=1,
+                              out_planes=x2_p)
+            engine.linear_fwd(ws, x2_p, w["w1" if big_ff else "w1_t"], ffn.linear_1.bias.data, None, M, F, E, act=1, out_z=z, out_planes=ff_p)
+            hn = mat("hn", M, E)
+            engine.linear_fwd(ws, ff_p, w["w2"], ffn.linear_2.bias.data, hn, M, E, F, resid=t1, drop=drop(s0 + 2))
+            S["x2_p"] = x2_p
+            return S, hn, None
+        inter, inter_p, S["m1"], S["r1"] = mat("inter", M, E), pl("inter_p", M, E), vec("m1", M), vec("r1", M)
+        ops.layernorm_fwd(t1, ln1.gamma.data, ln1.beta.data, inter, S["m1"], S["r1"], rows=M, D=E, eps=ln1.eps, mode=1,
+                          out_planes=inter_p)
+        engine.linear_fwd(ws, inter_p, w["w1" if big_ff else "w1_t"], ffn.linear_1.bias.data, None, M, F, E, act=1, out_z=z, out_planes=ff_p)
+        t2 = mat("t2", M, E)
+        engine.linear_fwd(ws, ff_p, w["w2"], ffn.linear_2.bias.data, t2, M, E, F, resid=inter, drop=drop(s0 + 2))
+        # a recomputed layer writes its output planes while its input planes (x_p: its QKV weight gradient reads them afterwards)
+        # must stay: two buffers, by layer parity (names matter to _Reused only)
+        hn, hn_p, S["m2"], S["r2"] = mat("hn", M, E), pl("h_p%d" % ((i + 1) & 1), M, E), vec("m2", M), vec("r2", M)
+        ops.layernorm_fwd(t2, ln2.gamma.data, ln2.beta.data, hn, S["m2"], S["r2"], rows=M, D=E, eps=ln2.eps, mode=1,
+                          out_planes=hn_p)
+        S.update(inter_p=inter_p, t2=t2)
+        return S, hn, hn_p
+
     @torch.no_grad()
     def _forward_train(self, emb, seg):
         if self.fp8_train:
             return self._forward_train_fp8(emb, seg)
-        B, L, E, H, hd, M, F = self._dims(emb)
+        dims = B, L, E, H, hd, M, F = self._dims(emb)
         dev = emb.device
         if self._ws is None or self._ws.device != dev:
             self._ws = engine.Workspace(dev)
-        ws = self._ws                                                   # split-K / reduction scratch only
         seg = seg.to(device=dev, dtype=torch.int64).contiguous().view(-1)
         W = self._weight_planes(dev, cache=False)
         p = float(self.transformer[0].dropout_1.p) if self.training else 0.0
         seed = runtime.next_drop(p, 0).seed if p > 0 else 0
         drop = (lambda site: ops.Drop(p, seed, site)) if p > 0 else (lambda site: None)
         pre = self.layernorm_positioning == "pre"
-        # everything the backward needs lives in one allocation per forward: per layer 32 (pre-LN) / 40 (post-LN) x M x E bytes
-        # of hidden-width tensors, 8 x M x F of feed-forward ones, 4 row statistics; + the final LayerNorm's statistics
-        per_layer = (32 if pre else 40) * M * E + 8 * M * F + 16 * M + 4 * B * H * L + 20 * 256
-        arena = engine.Arena(dev, self.layers_num * per_layer + 4 * M * E + 8 * M + 8 * 256)
-        mat, vec, pl = arena.mat, arena.vec, arena.planes
-        scale = 1.0 / math.sqrt(float(hd))
-        big_qkv, big_ff = ops.use_gemm256(M, 3 * E, E), ops.use_gemm256(M, F, E)
+        rc = bool(self.recompute)
+        # everything the backward needs lives in one allocation per forward
+        per_layer, tail = self._saved_bytes(B, L, rc)
+        kept = _Kept(dev, engine.Arena(dev, self.layers_num * per_layer + tail))
+        # recompute: only the layer outputs are kept (each the next layer's input); the rest lands in buffers every layer overwrites
+        A = _Reused(self, dev, "rc:", out=kept) if rc else kept
         h = emb.detach().contiguous().view(M, E)
         h_p = None
         if not pre:
-            h_p = ops.split_planes(h, pl(M, E))
-        saved = {"layers": [], "seg": seg, "dims": (B, L, E, H, hd, M, F), "drop": (p, seed), "W": W}
-        for i, (layer, w) in enumerate(zip(self.transformer, W)):
-            att, ffn = layer.self_attn, layer.feed_forward
-            ln1, ln2 = layer.layer_norm_1, layer.layer_norm_2
-            s0 = 4 * i
-            S = {}
-            if pre:
-                x_p, S["m1"], S["r1"], S["h_in"] = pl(M, E), vec(M), vec(M), h
-                ops.layernorm_fwd(h, ln1.gamma.data, ln1.beta.data, None, S["m1"], S["r1"], rows=M, D=E, eps=ln1.eps, mode=1,
-                                  out_planes=x_p)
-            else:
-                x_p = h_p
-            qkv_p, o_p, t1 = pl(M, 3 * E), pl(M, E), mat(M, E)
-            engine.linear_fwd(ws, x_p, w["wqkv" if big_qkv else "wqkv_t"], w["bqkv"], None, M, 3 * E, E, out_planes=qkv_p)
-            S["lse"] = vec(B * H * L)                                    # the attention's log-sum-exp: an input of its backward
-            ops.self_attn_fwd(qkv_p, seg, o_p, batch=B, heads=H, L=L, head_dim=hd, scale=scale, lse=S["lse"], drop=drop(s0))
-            engine.linear_fwd(ws, o_p, w["wo"], att.final_linear.bias.data, t1, M, E, E, resid=h, drop=drop(s0 + 1))
-            z, ff_p = mat(M, F), pl(M, F)
-            S.update(x_p=x_p, qkv_p=qkv_p, o_p=o_p, t1=t1, z=z, ff_p=ff_p)
-            if pre:
-                x2_p, S["m2"], S["r2"] = pl(M, E), vec(M), vec(M)
-                ops.layernorm_fwd(t1, ln2.gamma.data, ln2.beta.data, None, S["m2"], S["r2"], rows=M, D=E, eps=ln2.eps, mode=1,
-                                  out_planes=x2_p)
-                engine.linear_fwd(ws, x2_p, w["w1" if big_ff else "w1_t"], ffn.linear_1.bias.data, None, M, F, E, act=1, out_z=z, out_planes=ff_p)
-                hn = mat(M, E)
-                engine.linear_fwd(ws, ff_p, w["w2"], ffn.linear_2.bias.data, hn, M, E, F, resid=t1, drop=drop(s0 + 2))
-                S["x2_p"] = x2_p
-                h = hn
-            else:
-                inter, inter_p, S["m1"], S["r1"] = mat(M, E), pl(M, E), vec(M), vec(M)
-                ops.layernorm_fwd(t1, ln1.gamma.data, ln1.beta.data, inter, S["m1"], S["r1"], rows=M, D=E, eps=ln1.eps, mode=1,
-                                  out_planes=inter_p)
-                engine.linear_fwd(ws, inter_p, w["w1" if big_ff else "w1_t"], ffn.linear_1.bias.data, None, M, F, E, act=1, out_z=z, out_planes=ff_p)
-                t2 = mat(M, E)
-                engine.linear_fwd(ws, ff_p, w["w2"], ffn.linear_2.bias.data, t2, M, E, F, resid=inter, drop=drop(s0 + 2))
-                hn, hn_p, S["m2"], S["r2"] = mat(M, E), pl(M, E), vec(M), vec(M)
-                ops.layernorm_fwd(t2, ln2.gamma.data, ln2.beta.data, hn, S["m2"], S["r2"], rows=M, D=E, eps=ln2.eps, mode=1,
-                                  out_planes=hn_p)
-                S.update(inter_p=inter_p, t2=t2)
-                h, h_p = hn, hn_p
-            saved["layers"].append(S)
+            h_p = ops.split_planes(h, A.planes("h_p0", M, E))
+        saved = {"layers": [], "seg": seg, "dims": dims, "drop": (p, seed), "W": W, "recompute": rc}
+        for i, w in enumerate(W):
+            S, hn, hn_p = self._layer_fwd_train(i, w, h, h_p, A, seg, dims, drop)
+            saved["layers"].append({"h_in": h} if rc else S)
+            h, h_p = hn, hn_p
         if self.final_layernorm:
             out = torch.empty(B, L, E, device=dev)
-            saved["h_final"], saved["mf"], saved["rf"] = h, vec(M), vec(M)
+            saved["h_final"], saved["mf"], saved["rf"] = h, kept.vec("mf", M), kept.vec("rf", M)
             ops.layernorm_fwd(h, self.layer_norm.gamma.data, self.layer_norm.beta.data, out.view(M, E), saved["mf"], saved["rf"],
                               rows=M, D=E, eps=self.layer_norm.eps, mode=1)
         else:
@@ -502,8 +583,16 @@ class TransformerEncoder(nn.Module):
             dh = dnew
         dff_ready = pre and self.final_layernorm
         flip = 1
+        rc = _Reused(self, dev, "rc:") if saved.get("recompute") else None
         for i in reversed(range(self.layers_num)):
             layer, w, S = self.transformer[i], W[i], saved["layers"][i]
+            if rc is not None:
+                # the layer's forward again, from its saved input: the forward's seed (no draw: the counter stays where the plain
+                # path leaves it), sites and weight operands -> the same bits; its output is dropped.  Post-LN: the input planes
+                # are the split of the input, as the LayerNorm below wrote them (same rounding of the same fp32 values)
+                h_in = S["h_in"]
+                h_p = None if pre else ops.split_planes(h_in, rc.planes("h_p%d" % (i & 1), M, E))
+                S = self._layer_fwd_train(i, w, h_in, h_p, rc, seg, saved["dims"], drop)[0]
             att, ffn = layer.self_attn, layer.feed_forward
             ln1, ln2 = layer.layer_norm_1, layer.layer_norm_2
             s0 = 4 * i
@@ -586,34 +675,26 @@ class TransformerEncoder(nn.Module):
             m = bufs[name] = ops.Mx8.empty(rows, cols, dev)
         return m
 
-    @torch.no_grad()
-    def _forward_train_fp8(self, emb, seg, save: bool = True):
-        """save=False (a forward no backward follows: extract(), eval and rollout forwards): the same arithmetic and the same output
-        bits, but the activations live in reused workspace buffers and the column-blocked copies are not written."""
-        B, L, E, H, hd, M, F = self._dims(emb)
-        if E % 128 or F % 128:
-            raise ValueError("mxfp8_train: hidden and feed-forward widths must be multiples of 128")
-        dev = emb.device
-        if self._ws is None or self._ws.device != dev:
-            self._ws = engine.Workspace(dev)
-        ws = self._ws
-        seg = seg.to(device=dev, dtype=torch.int64).contiguous().view(-1)
-        W = self._fp8_train_weights()
-        p = float(self.transformer[0].dropout_1.p) if self.training else 0.0
-        seed = runtime.next_drop(p, 0).seed if p > 0 else 0
-        drop = (lambda site: ops.Drop(p, seed, site)) if p > 0 else (lambda site: None)
+    def _layer_fwd_train_fp8(self, i, w, h, A, seg, dims, drop, transposed):
+        """Layer i of the MX-FP8 training schedule.  h: the layer's input [M, E]; A: the allocator of what the layer writes (_Kept:
+        fresh tensors; _Reused: workspace buffers); transposed: also write the column-blocked copies the weight gradients read.
+        -> (S: what the layer's backward reads, the layer's output)."""
+        B, L, E, H, hd, M, F = dims
+        ws, dev = self._ws, h.device
+        layer = self.transformer[i]
+        att, ffn = layer.self_attn, layer.feed_forward
+        ln1, ln2 = layer.layer_norm_1, layer.layer_norm_2
         pre = self.layernorm_positioning == "pre"
         scale = 1.0 / math.sqrt(float(hd))
+        Mp = -(-M // 128) * 128
         xs, ys = ws.mat("fp8t_x", M, E), ws.mat("fp8t_y", M, E)        # transient fp32: LayerNorm output, projection before dropout
         x_q, f_q = self._mx("fx", M, E, dev), self._mx("ff", M, F, dev)  # transient row-blocked A operands
-        # what the backward reads: fresh tensors when saving, else named workspace buffers (the layer output alternates between two)
-        mat = (lambda name, r, c: torch.empty(r, c, device=dev)) if save else (lambda name, r, c: ws.mat("fp8e:" + name, r, c))
-        vec = (lambda name, n: torch.empty(n, device=dev)) if save else (lambda name, n: ws.vec("fp8e:" + name, n))
-        pl = (lambda name, r, c: ops.Planes.empty(r, c, dev)) if save else (lambda name, r, c: ws.planes("fp8e:" + name, r, c))
+        mat, vec, pl = A.mat, A.vec, A.planes
 
-        def quant(x, a_q, act=0):
-            """row-blocked a_q of x (GELU(x) with act 1), and, when saving, the column-blocked copy of x^T the weight gradient reads"""
-            return ops.quant_mxfp8_t(x, rows_out=a_q, act=act, transposed=save)[0]
+        def quant(name, x, a_q, act=0):
+            """row-blocked a_q of x (GELU(x) with act 1), and, when asked, the column-blocked copy of x^T the weight gradient reads"""
+            return ops.quant_mxfp8_t(x, rows_out=a_q, act=act, transposed=transposed,
+                                     dst=A.mx_t(name, a_q.cols, Mp) if transposed else None)[0]
 
         def proj_out(a_q, wq, bias, resid, out, site):
             """out = resid + dropout(a . W^T + bias): the split-bf16 epilogue's order"""
@@ -623,53 +704,75 @@ class TransformerEncoder(nn.Module):
                 ops.gemm_mxfp8(a_q, wq, ys, bias=bias)
                 ops.dropout_residual(ys, resid, out, site)
 
+        s0 = 4 * i
+        S = {}
+        if pre:
+            S["m1"], S["r1"], S["h_in"] = vec("m1", M), vec("r1", M), h
+            ops.layernorm_fwd(h, ln1.gamma.data, ln1.beta.data, xs, S["m1"], S["r1"], rows=M, D=E, eps=ln1.eps, mode=1)
+            S["xT"] = quant("xT", xs, x_q)
+        else:
+            S["xT"] = quant("xT", h, x_q)
+        qkv_p, o_p = pl("qkv", M, 3 * E), pl("o", M, E)
+        ops.gemm_mxfp8(x_q, w["wqkv"], None, bias=w["bqkv"], out_planes=qkv_p)
+        S["lse"] = vec("lse", B * H * L)
+        ops.self_attn_fwd(qkv_p, seg, o_p, batch=B, heads=H, L=L, head_dim=hd, scale=scale, lse=S["lse"], drop=drop(s0))
+        S["oT"] = quant("oT", o_p, x_q)
+        t1 = mat("t1", M, E)
+        proj_out(x_q, w["wo"], att.final_linear.bias.data, h, t1, drop(s0 + 1))
+        z = mat("z", M, F)
+        S.update(qkv_p=qkv_p, o_p=o_p, t1=t1, z=z)
+        hn = mat("hn%d" % (i & 1), M, E)                                # reused buffers: the layer output alternates between two
+        if pre:
+            S["m2"], S["r2"] = vec("m2", M), vec("r2", M)
+            ops.layernorm_fwd(t1, ln2.gamma.data, ln2.beta.data, xs, S["m2"], S["r2"], rows=M, D=E, eps=ln2.eps, mode=1)
+            S["x2T"] = quant("x2T", xs, x_q)
+            ops.gemm_mxfp8(x_q, w["w1"], z, bias=ffn.linear_1.bias.data)
+            S["ffT"] = quant("ffT", z, f_q, act=1)
+            proj_out(f_q, w["w2"], ffn.linear_2.bias.data, t1, hn, drop(s0 + 2))
+        else:
+            inter, S["m1"], S["r1"] = mat("inter", M, E), vec("m1", M), vec("r1", M)
+            ops.layernorm_fwd(t1, ln1.gamma.data, ln1.beta.data, inter, S["m1"], S["r1"], rows=M, D=E, eps=ln1.eps, mode=1)
+            S["x2T"] = quant("x2T", inter, x_q)
+            ops.gemm_mxfp8(x_q, w["w1"], z, bias=ffn.linear_1.bias.data)
+            S["ffT"] = quant("ffT", z, f_q, act=1)
+            t2 = mat("t2", M, E)
+            proj_out(f_q, w["w2"], ffn.linear_2.bias.data, inter, t2, drop(s0 + 2))
+            S["m2"], S["r2"] = vec("m2", M), vec("r2", M)
+            ops.layernorm_fwd(t2, ln2.gamma.data, ln2.beta.data, hn, S["m2"], S["r2"], rows=M, D=E, eps=ln2.eps, mode=1)
+            S["t2"] = t2
+        return S, hn
+
+    @torch.no_grad()
+    def _forward_train_fp8(self, emb, seg, save: bool = True):
+        """save=False (a forward no backward follows: extract(), eval and rollout forwards): the same arithmetic and the same output
+        bits, but the activations live in reused workspace buffers and the column-blocked copies are not written.  With `recompute` a
+        saving forward runs that way too and keeps only each layer's input (the previous layer's output, a tensor of its own)."""
+        dims = B, L, E, H, hd, M, F = self._dims(emb)
+        if E % 128 or F % 128:
+            raise ValueError("mxfp8_train: hidden and feed-forward widths must be multiples of 128")
+        dev = emb.device
+        if self._ws is None or self._ws.device != dev:
+            self._ws = engine.Workspace(dev)
+        seg = seg.to(device=dev, dtype=torch.int64).contiguous().view(-1)
+        W = self._fp8_train_weights()
+        p = float(self.transformer[0].dropout_1.p) if self.training else 0.0
+        seed = runtime.next_drop(p, 0).seed if p > 0 else 0
+        drop = (lambda site: ops.Drop(p, seed, site)) if p > 0 else (lambda site: None)
+        rc = save and bool(self.recompute)
+        # what the backward reads: fresh tensors when saving, else named workspace buffers
+        kept = _Kept(dev)
+        A = kept if save and not rc else _Reused(self, dev, "fp8e:", out=kept if rc else None)
         h = emb.detach().contiguous().view(M, E)
-        saved = {"fp8": True, "layers": [], "seg": seg, "dims": (B, L, E, H, hd, M, F), "drop": (p, seed), "W": W}
-        for i, (layer, w) in enumerate(zip(self.transformer, W)):
-            att, ffn = layer.self_attn, layer.feed_forward
-            ln1, ln2 = layer.layer_norm_1, layer.layer_norm_2
-            s0 = 4 * i
-            S = {}
-            if pre:
-                S["m1"], S["r1"], S["h_in"] = vec("m1", M), vec("r1", M), h
-                ops.layernorm_fwd(h, ln1.gamma.data, ln1.beta.data, xs, S["m1"], S["r1"], rows=M, D=E, eps=ln1.eps, mode=1)
-                S["xT"] = quant(xs, x_q)
-            else:
-                S["xT"] = quant(h, x_q)
-            qkv_p, o_p = pl("qkv", M, 3 * E), pl("o", M, E)
-            ops.gemm_mxfp8(x_q, w["wqkv"], None, bias=w["bqkv"], out_planes=qkv_p)
-            S["lse"] = vec("lse", B * H * L)
-            ops.self_attn_fwd(qkv_p, seg, o_p, batch=B, heads=H, L=L, head_dim=hd, scale=scale, lse=S["lse"], drop=drop(s0))
-            S["oT"] = quant(o_p, x_q)
-            t1 = mat("t1", M, E)
-            proj_out(x_q, w["wo"], att.final_linear.bias.data, h, t1, drop(s0 + 1))
-            z = mat("z", M, F)
-            S.update(qkv_p=qkv_p, o_p=o_p, t1=t1, z=z)
-            hn = mat("h%d" % (i & 1), M, E)
-            if pre:
-                S["m2"], S["r2"] = vec("m2", M), vec("r2", M)
-                ops.layernorm_fwd(t1, ln2.gamma.data, ln2.beta.data, xs, S["m2"], S["r2"], rows=M, D=E, eps=ln2.eps, mode=1)
-                S["x2T"] = quant(xs, x_q)
-                ops.gemm_mxfp8(x_q, w["w1"], z, bias=ffn.linear_1.bias.data)
-                S["ffT"] = quant(z, f_q, act=1)
-                proj_out(f_q, w["w2"], ffn.linear_2.bias.data, t1, hn, drop(s0 + 2))
-            else:
-                inter, S["m1"], S["r1"] = mat("inter", M, E), vec("m1", M), vec("r1", M)
-                ops.layernorm_fwd(t1, ln1.gamma.data, ln1.beta.data, inter, S["m1"], S["r1"], rows=M, D=E, eps=ln1.eps, mode=1)
-                S["x2T"] = quant(inter, x_q)
-                ops.gemm_mxfp8(x_q, w["w1"], z, bias=ffn.linear_1.bias.data)
-                S["ffT"] = quant(z, f_q, act=1)
-                t2 = mat("t2", M, E)
-                proj_out(f_q, w["w2"], ffn.linear_2.bias.data, inter, t2, drop(s0 + 2))
-                S["m2"], S["r2"] = vec("m2", M), vec("r2", M)
-                ops.layernorm_fwd(t2, ln2.gamma.data, ln2.beta.data, hn, S["m2"], S["r2"], rows=M, D=E, eps=ln2.eps, mode=1)
-                S["t2"] = t2
-            h = hn
+        saved = {"fp8": True, "layers": [], "seg": seg, "dims": dims, "drop": (p, seed), "W": W, "recompute": rc}
+        for i, w in enumerate(W):
+            S, hn = self._layer_fwd_train_fp8(i, w, h, A, seg, dims, drop, transposed=save and not rc)
             if save:
-                saved["layers"].append(S)
+                saved["layers"].append({"h_in": h} if rc else S)
+            h = hn
         if self.final_layernorm:
             out = torch.empty(B, L, E, device=dev)
-            mf, rf = vec("mf", M), vec("rf", M)
+            fin = kept if save else A
+            mf, rf = fin.vec("mf", M), fin.vec("rf", M)
             ops.layernorm_fwd(h, self.layer_norm.gamma.data, self.layer_norm.beta.data, out.view(M, E), mf, rf,
                               rows=M, D=E, eps=self.layer_norm.eps, mode=1)
             saved["h_final"], saved["mf"], saved["rf"] = h, mf, rf
@@ -726,8 +829,11 @@ class TransformerEncoder(nn.Module):
             dh = dnew
         dff_ready = pre and self.final_layernorm
         flip = 1
+        rc = _Reused(self, dev, "fp8e:") if saved.get("recompute") else None
         for i in reversed(range(self.layers_num)):
             layer, w, S = self.transformer[i], W[i], saved["layers"][i]
+            if rc is not None:          # the saving forward of this layer alone (see _backward_train); W: the forward's quantised weights
+                S = self._layer_fwd_train_fp8(i, w, S["h_in"], rc, seg, saved["dims"], drop, transposed=True)[0]
             att, ffn = layer.self_attn, layer.feed_forward
             ln1, ln2 = layer.layer_norm_1, layer.layer_norm_2
             s0 = 4 * i

@@ -1,6 +1,7 @@
 """Dual-encoder forward micro-benchmark (ViT-B/16 + RoBERTa-base, random weights, batch 32 of the repo's default shapes).
 Prints ms per forward, algorithmic TFLOP/s (2MNK of the GEMMs + 4 L^2 d of attention) and a per-kernel-class breakdown
-from HIP events.  python tools/encoder_bench.py [--batch 32] [--iters 10] [--passes 3]"""
+from HIP events.  python tools/encoder_bench.py [--batch 32] [--iters 10] [--passes 3]
+--train [--precision mxfp8_train] [--recompute]: forward + backward per step, and the step's peak device memory."""
 import argparse
 import os
 import sys
@@ -86,7 +87,12 @@ def main():
                     "--ppo-shapes: both towers at the PPO sizes (ViT over batch*16 frames, RoBERTa over batch*2 sequences)")
     ap.add_argument("--precision", choices=("split_bf16", "mxfp8_train"), default="split_bf16",
                     help="--train: the encoders' training precision (TransformerEncoder.fp8_train)")
+    ap.add_argument("--recompute", action="store_true",
+                    help="--train: keep each layer's input only and re-run a layer's forward in front of its backward "
+                         "(TransformerEncoder.recompute); the peak-memory figure shows what that buys, the step time what it costs")
     a = ap.parse_args()
+    if a.recompute and not a.train:
+        ap.error("--recompute is a switch of the training schedule: give --train")
     dev = torch.device("cuda:0")
     ops.set_gemm_passes(a.passes)
     torch.manual_seed(0)
@@ -103,6 +109,7 @@ def main():
         enc = enc.to(dev)
         enc = enc.train() if a.train else enc.eval()
         enc.fp8_train = a.train and a.precision == "mxfp8_train"
+        enc.recompute = a.recompute
         B = (a.batch * 16 if name.startswith("vit") else a.batch * 2) if a.ppo_shapes else a.batch
         emb = torch.randn(B, L, 768, device=dev, requires_grad=a.train)
         seg = torch.ones(B, L, dtype=torch.int64, device=dev)
@@ -117,6 +124,8 @@ def main():
         for _ in range(2):
             run()
         torch.cuda.synchronize()
+        resident = torch.cuda.memory_allocated()                      # parameters, gradients, workspace, inputs
+        torch.cuda.reset_peak_memory_stats()
         s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         s.record()
         for _ in range(a.iters):
@@ -124,6 +133,7 @@ def main():
         e.record()
         torch.cuda.synchronize()
         ms = s.elapsed_time(e) / a.iters
+        peak = torch.cuda.max_memory_allocated()
         fl = flops(B, L) * (3.0 if a.train else 1.0)
         total_ms += ms
         total_fl += fl
@@ -136,6 +146,10 @@ def main():
             classes[c] = classes.get(c, 0.0) + v["ms"]
         print(f"{name:13s} B={B} L={L} {a.precision if a.train else ''}: {ms:7.3f} ms/{'step' if a.train else 'forward'}  {fl / ms / 1e9:7.1f} TFLOP/s (algorithmic)  "
               f"frac of 2.5 PF bf16 dense x{a.passes} passes: {a.passes * fl / ms / 1e9 / 2500:.3f}", flush=True)
+        if a.train:
+            print(f"    recompute {'on' if a.recompute else 'off'}: peak memory {peak / 2 ** 30:.2f} GiB ({(peak - resident) / 2 ** 30:.2f} GiB above "
+                  f"the resident {resident / 2 ** 30:.2f}); saved activations by the formula {enc.saved_activation_bytes(B, L) / 2 ** 30:.2f} GiB",
+                  flush=True)
         print("    events:", {k: round(v, 3) for k, v in sorted(classes.items(), key=lambda kv: -kv[1])}, flush=True)
         if a.detail:
             for k, v in sorted(prof.items(), key=lambda kv: -kv[1]["ms"]):
