@@ -121,17 +121,23 @@ int lr2_gather_rows_bwd(const void* ddst, const int64_t* index, void* dsrc, int 
  * replaces: torch.cat([x, img_feature], dim=1) (finetune/ppo.py:224). */
 int lr2_copy_rows(const void* src, void* dst, int dst_planes, uint64_t dst_lo_off, int rows, int D, int group,
                   uint64_t dst_gstride, uint64_t dst_off, void* stream);
-/* fp32 -> bf16 planes: dst_hi[i] = bf16(src[i]), dst_hi[lo_off + i] = bf16(src[i] - hi) for i < n (n % 4 == 0). */
+/* fp32 -> bf16 planes: dst_hi[i] = bf16(src[i]), dst_hi[lo_off + i] = bf16(src[i] - hi) for i < n (n % 4 == 0).
+ * Vector accesses: src 16-byte aligned, dst_hi 8-byte aligned, lo_off % 4 == 0 (the lo plane 8-byte aligned too), else
+ * LR2_ERR_SHAPE. */
 int lr2_split_planes(const void* src, void* dst_hi, uint64_t lo_off, uint64_t n, void* stream);
 /* Transposing split: src fp32 [R][C] -> planes [C][R] (hi at dst_hi, lo lo_off elements behind).  An nn.Linear weight
  * [out, in] re-laid as [in, out] lets its forward x.W^T run as the (0,1) form of lr2_gemm, the fastest of the three on wide
- * outputs; nothing in the reference corresponds to it (layout choice of this build). */
+ * outputs; nothing in the reference corresponds to it (layout choice of this build).  Element-wise accesses only: no alignment
+ * beyond the element types', any lo_off. */
 int lr2_split_planes_t(const void* src, void* dst_hi, uint64_t lo_off, int R, int C, void* stream);
 /* planes of dropout_mask(src) / (1 - p), mask element index = flat element index (the gradient entering a dropped branch).
+ * drop_p in [0, 1) (0: lr2_split_planes); n % 4 == 0; src 16-byte aligned, dst_hi 8-byte aligned, lo_off % 4 == 0, else LR2_ERR_SHAPE.
  * replaces: autograd of nn.Dropout at tencentpretrain/layers/transformer.py:55,58,65,72 on the pre-LN residual paths. */
 int lr2_dropout_planes(const void* src, void* dst_hi, uint64_t lo_off, uint64_t n, float drop_p, uint64_t drop_seed,
                        uint32_t drop_site, void* stream);
-/* The same for many tensors in one launch (weights after an optimizer step). table: DEVICE array of chunks. */
+/* lr2_split_planes for many tensors in one launch (weights after an optimizer step). table: DEVICE array of chunks.  The table
+ * lives on the device, so the chunks are NOT checked: each must meet lr2_split_planes' rules (src 16-byte aligned, dst_hi 8-byte
+ * aligned, lo_off % 4 == 0, count % 4 == 0). */
 typedef struct lr2_split_chunk {
   const void* src;
   void* dst_hi;
@@ -265,6 +271,7 @@ int lr2_ppo_loss(const void* scores, const void* old_scores, const void* rewards
 
 /* mode = 'cls' (C classes, C <= 8): the 768 -> C head, y[r, c] = x[r, :] . w[c, :] + b[c], and its backward
  * (dx[r, :] = sum_c dy[r, c] w[c, :]; dw[c, :] = sum_r dy[r, c] x[r, :]; db[c] = sum_r dy[r, c]; dx or dw/db may be NULL).
+ * D % 4 == 0; x and w (forward), w and dx (backward, when dx is given) 16-byte aligned, else LR2_ERR_SHAPE.
  * replaces: nn.Linear(768, labels_num) of finetune/ppo.py:209-210,228-230 and its autograd. */
 int lr2_cls_head_fwd(const void* x, const void* w, const void* b, void* y, int rows, int D, int C, void* stream);
 int lr2_cls_head_bwd(const void* x, const void* w, const void* dy, void* dx, void* dw, void* db, int rows, int D, int C,
@@ -332,6 +339,7 @@ int lr2_text_embed_bwd(const void* dx, const int64_t* sorted_ids, const int64_t*
                        void* dseg, void* seg_partials, void* word_partials, int rows, int D, int64_t vocab, int n_seg,
                        void* stream);
 /* dst = dropout_mask(src) / (1 - p), fp32, mask element index = flat element index (src == dst allowed).
+ * drop_p in (0, 1); n % 4 == 0; src and dst 16-byte aligned, else LR2_ERR_SHAPE.
  * replaces: self.dropout of tencentpretrain/embeddings/embedding.py:33 and its autograd. */
 int lr2_dropout_apply(const void* src, void* dst, uint64_t n, float drop_p, uint64_t drop_seed, uint32_t drop_site,
                       void* stream);

@@ -530,13 +530,15 @@ __global__ __launch_bounds__(1024) void nll_loss_kernel(const float* __restrict_
     float mx = -INFINITY, sum = 0.f;
     for (int c = 0; c < C; ++c) mx = fmaxf(mx, logits[(size_t)r * C + c]);
     for (int c = 0; c < C; ++c) sum += expf(logits[(size_t)r * C + c] - mx);
-    const float lz = mx + logf(sum);
+    // everything on the SHIFTED logits z - mx: forming mx + log(sum) first rounds it to an ulp of |mx| (8e-6 at |z| = 80), and that
+    // absolute error would then sit in a loss term and in the exponent of every probability of the row
+    const float ls = logf(sum);
     int t = (int)tgts[r];
     t = t < 0 ? 0 : (t >= C ? C - 1 : t);
-    acc += lz - logits[(size_t)r * C + t];
+    acc += ls - (logits[(size_t)r * C + t] - mx);
     if (dlogits)
       for (int c = 0; c < C; ++c)
-        dlogits[(size_t)r * C + c] = (expf(logits[(size_t)r * C + c] - lz) - (c == t ? 1.f : 0.f)) / (float)rows;
+        dlogits[(size_t)r * C + c] = (expf((logits[(size_t)r * C + c] - mx) - ls) - (c == t ? 1.f : 0.f)) / (float)rows;
   }
   const float s = block_sum_1024(acc, red);
   if (threadIdx.x == 0) loss[0] = s / (float)rows;
@@ -804,6 +806,8 @@ inline int grid_for(size_t work_items, int cap = 4096) {
   return (int)b;
 }
 #define CHECK_LAUNCH() return lr2_launch_status(__func__)
+// a pointer that a kernel's vector access (float4: 16 bytes, 4 x bf16: 8 bytes) cannot take: LR2_ERR_SHAPE, never a launch
+inline bool misaligned(const void* p, uintptr_t bytes) { return ((uintptr_t)p % bytes) != 0; }
 
 }  // namespace
 
@@ -854,6 +858,7 @@ extern "C" int lr2_copy_rows(const void* src, void* dst, int dst_planes, uint64_
 extern "C" int lr2_split_planes(const void* src, void* dst_hi, uint64_t lo_off, uint64_t n, void* stream) {
   if (!src || !dst_hi || n == 0) return LR2_ERR_ARG;
   if (n % 4 || lo_off % 4) return LR2_ERR_SHAPE;
+  if (misaligned(src, 16) || misaligned(dst_hi, 8)) return LR2_ERR_SHAPE;       // float4 loads, 4 x bf16 stores per plane
   LR2_LAUNCH(split_planes_kernel, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, (const float*)src,
              (bf16_t*)dst_hi, (size_t)lo_off, (size_t)(n / 4));
   CHECK_LAUNCH();
@@ -863,6 +868,7 @@ extern "C" int lr2_dropout_planes(const void* src, void* dst_hi, uint64_t lo_off
                                   uint32_t drop_site, void* stream) {
   if (!src || !dst_hi || n == 0 || drop_p < 0.f || drop_p >= 1.f) return LR2_ERR_ARG;
   if (n % 4 || lo_off % 4) return LR2_ERR_SHAPE;
+  if (misaligned(src, 16) || misaligned(dst_hi, 8)) return LR2_ERR_SHAPE;       // float4 loads, 4 x bf16 stores per plane
   if (drop_p == 0.f) return lr2_split_planes(src, dst_hi, lo_off, n, stream);
   LR2_LAUNCH(dropout_planes_kernel, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, (const float*)src,
              (bf16_t*)dst_hi, (size_t)lo_off, (size_t)(n / 4), 1.0f / (1.0f - drop_p), dropout_threshold(drop_p),
@@ -873,7 +879,7 @@ extern "C" int lr2_dropout_planes(const void* src, void* dst_hi, uint64_t lo_off
 extern "C" int lr2_dropout_apply(const void* src, void* dst, uint64_t n, float drop_p, uint64_t drop_seed, uint32_t drop_site,
                                  void* stream) {
   if (!src || !dst || n == 0 || drop_p <= 0.f || drop_p >= 1.f) return LR2_ERR_ARG;
-  if (n % 4) return LR2_ERR_SHAPE;
+  if (n % 4 || misaligned(src, 16) || misaligned(dst, 16)) return LR2_ERR_SHAPE;      // float4 loads and stores
   LR2_LAUNCH(dropout_apply_kernel, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, (const float*)src, (float*)dst,
              (size_t)(n / 4), 1.0f / (1.0f - drop_p), dropout_threshold(drop_p),
              (((uint64_t)drop_site) << 40) ^ (drop_seed * 0x9E3779B97F4A7C15ull));
@@ -982,6 +988,7 @@ extern "C" int lr2_ppo_loss(const void* scores, const void* old_scores, const vo
 extern "C" int lr2_cls_head_fwd(const void* x, const void* w, const void* b, void* y, int rows, int D, int C, void* stream) {
   if (!x || !w || !b || !y || rows <= 0) return LR2_ERR_ARG;
   if (D % 4 || C < 1 || C > CLS_MAX_C) return LR2_ERR_SHAPE;
+  if (misaligned(x, 16) || misaligned(w, 16)) return LR2_ERR_SHAPE;             // float4 loads of the rows of x and w
   LR2_LAUNCH(cls_head_fwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const float*)x, (const float*)w,
              (const float*)b, (float*)y, rows, D, C);
   CHECK_LAUNCH();
@@ -991,6 +998,7 @@ extern "C" int lr2_cls_head_bwd(const void* x, const void* w, const void* dy, vo
                                 void* stream) {
   if (!x || !w || !dy || rows <= 0) return LR2_ERR_ARG;
   if (D % 4 || C < 1 || C > CLS_MAX_C) return LR2_ERR_SHAPE;
+  if (dx && (misaligned(w, 16) || misaligned(dx, 16))) return LR2_ERR_SHAPE;    // the dx kernel's float4 accesses (dw / db: scalar)
   hipStream_t s = (hipStream_t)stream;
   if (dx) {
     LR2_LAUNCH(cls_head_bwd_dx_kernel, dim3(grid_for((size_t)rows * D / 4)), dim3(256), 0, s, (const float*)w, (const float*)dy,

@@ -132,6 +132,125 @@ def test_wgrad_product_on_random_data(dev):
     assert torch.equal(out, out2)
 
 
+def _fixed_blocks(x):
+    """Four fixed 32-element MX blocks written into x [R, C], each once down a column (rows [0, 32) of columns 1, 3, 5, 7: a block of
+    x^T, cut short by a smaller R) and once along a row (row 7 j mod R, a 32-column block behind the first one, where R and C leave
+    room): amax exactly 2^3; amax = 1.9999 x 2^-5, which the shared scale takes to 511.97 > 448 (it must saturate at 448, not wrap);
+    every element below FLT_MIN (scale byte 0, the values still resolved); amax = 2^127."""
+    R, C = x.shape
+    g = torch.Generator().manual_seed(R * 1000 + C)
+    u = lambda: torch.rand(32, generator=g) * 2 - 1          # noqa: E731
+    blocks = []
+    for lead, rest in ((8.0, 8.0), (1.9999 * 2.0 ** -5, 2.0 ** -6), (1.1e-38, 1e-39), (2.0 ** 127, 2.0 ** 120)):
+        v = u() * rest
+        v[0] = lead                     # first, so that a block cut short by R < 32 still holds its amax
+        blocks.append(v)
+    n = min(32, R)
+    used = set()
+    for j, v in enumerate(blocks):
+        x[:n, 2 * j + 1] = v[:n]
+        spot = ((7 * j) % R, 1 + j % (C // 32 - 1))
+        if spot not in used:
+            used.add(spot)
+            x[spot[0], 32 * spot[1]:32 * spot[1] + 32] = v
+    return x
+
+
+def _inside_nan(x, left, right, dev):
+    """x as a column slice of a wider NaN-filled matrix on the device: row stride > cols, a 16-byte-aligned offset"""
+    big = torch.full((x.shape[0], left + x.shape[1] + right), float("nan"))
+    big[:, left:left + x.shape[1]] = x
+    view = big.to(dev)[:, left:left + x.shape[1]]
+    assert view.stride(0) > x.shape[1] and view.data_ptr() % 16 == 0
+    return view
+
+
+@pytest.mark.parametrize("C", [64, 192])
+@pytest.mark.parametrize("R", [1, 31, 32, 33, 127, 128, 129, 394])
+def test_quantiser_argument_forms_and_fixed_blocks(dev, R, C):
+    """The forms of lr2_quant_mxfp8_t beside the dense fp32 one, at row counts around the 32-row block and the 128-row tile: a strided
+    source, a strided z, no transposed output, planes through a prologue, accumulated column sums through an oversized workspace.
+    Bytes and scale bytes equal the MX rule (or, behind a GELU prologue whose erf is the kernels' own, the dense form's)."""
+    from lr2ppo_amd import ops
+    g = torch.Generator().manual_seed(R * 7 + C)
+    x = _fixed_blocks((torch.randn(R, C, generator=g) + 0.25) * torch.exp(torch.randn(1, C, generator=g) * 2))
+    xs = _inside_nan(x, 64, 64, dev)
+    Rp = -(-R // 128) * 128
+    # strided source -> x^T and the row-blocked form, against the rule; padding bytes and padding scale bytes zero
+    mt, mr, _ = ops.quant_mxfp8_t(xs, row_blocked=True)
+    assert (mt.rows, mt.cols, mr.rows, mr.cols) == (C, Rp, R, C)
+    q_ref, s_ref = _ref_quant(_padded_t(x))
+    qt, st = mt.q.view(C, Rp).cpu(), mt.s.view(C, Rp // 32).cpu()
+    assert torch.equal(st, s_ref)
+    same = _same_bytes(qt, q_ref)
+    assert bool(same.all()), f"x^T: {int((~same).sum())} of {C * Rp} bytes differ"
+    assert bool((qt[:, R:] == 0).all()) and bool((st[:, -(-R // 32):] == 0).all())
+    qr_ref, sr_ref = _ref_quant(x)
+    assert torch.equal(mr.s.view(R, C // 32).cpu(), sr_ref)
+    same = _same_bytes(mr.q.view(R, C).cpu(), qr_ref)
+    assert bool(same.all()), f"rows: {int((~same).sum())} of {R * C} bytes differ"
+    row = ops.quant_mxfp8(x.to(dev))
+    assert torch.equal(mr.q, row.q) and torch.equal(mr.s, row.s)
+    # the fixed blocks did what they are there for
+    assert int(st[1, 0]) == 127 + 3 - 8 and int(st[5, 0]) == 0 and int(st[7, 0]) == 127 + 127 - 8
+    assert int(qt[3, 0]) == 0x7E and int(st[3, 0]) == 127 - 5 - 8              # 1.9999 x 2^-5 -> +448, saturated
+    # no transposed output: rows_out alone
+    r2 = ops.Mx8.empty(R, C, dev)
+    none, got, _ = ops.quant_mxfp8_t(xs, rows_out=r2, transposed=False)
+    assert none is None and got is r2 and torch.equal(r2.q, mr.q) and torch.equal(r2.s, mr.s)
+    # prologues, on plain data (a product with GELU'(z) beside 2^127 would overflow): x * GELU'(z) with x and z both strided = the
+    # dense form; planes through GELU = the fp32 form of hi + lo
+    y, z = torch.randn(R, C, generator=g), torch.randn(R, C, generator=g) * 2
+    yd, ys = y.to(dev), _inside_nan(y, 64, 0, dev)
+    a, ar, _ = ops.quant_mxfp8_t(yd, act=2, z=z.to(dev), row_blocked=True)
+    b, br, _ = ops.quant_mxfp8_t(ys, act=2, z=_inside_nan(z, 32, 96, dev), row_blocked=True)
+    assert torch.equal(a.q, b.q) and torch.equal(a.s, b.s) and torch.equal(ar.q, br.q) and torch.equal(ar.s, br.s)
+    plain = ops.quant_mxfp8_t(yd)[0]
+    assert not torch.equal(a.q, plain.q)
+    pl = ops.Planes.empty(R, C, dev)
+    ops.split_planes(yd, pl)
+    a, ar, _ = ops.quant_mxfp8_t(pl, act=1, row_blocked=True)
+    b, br, _ = ops.quant_mxfp8_t(pl.to_float().contiguous(), act=1, row_blocked=True)
+    assert torch.equal(a.q, b.q) and torch.equal(a.s, b.s) and torch.equal(ar.q, br.q) and torch.equal(ar.s, br.s)
+    assert not torch.equal(a.q, ops.quant_mxfp8_t(pl)[0].q)
+    # column sums: written, then added to a prefilled vector through a workspace larger than rows_pad / 128 * cols
+    written = torch.full((C,), float("nan"), device=dev)
+    ops.quant_mxfp8_t(ys, colsum=written)
+    err = (written.double().cpu() - y.double().sum(0)).abs()
+    assert bool((err <= (R + 2) * 2.0 ** -24 * y.double().abs().sum(0)).all())      # an fp32 sum of R terms in any order
+    pre = torch.randn(C, generator=g).to(dev)
+    acc = pre.clone()
+    used = (Rp // 128) * C
+    partials = torch.full((used + 1000,), float("nan"), device=dev)
+    ops.quant_mxfp8_t(ys, colsum=acc, accumulate=True, partials=partials)
+    assert torch.equal(acc, pre + written)
+    assert bool(torch.isfinite(partials[:used]).all()) and bool(torch.isnan(partials[used:]).all())
+
+
+@pytest.mark.parametrize("splits", [1, 2, 4, 8, 64])
+@pytest.mark.parametrize("M,N,K", [(128, 128, 128), (128, 256, 640), (384, 128, 1152)])
+def test_wgrad_slice_counts_and_strided_destination(dev, M, N, K, splits):
+    """Slice counts beyond K / 128 (capped) and ones the step count does not divide (K = 640, 4 slices asked: 3 of 2, 2 and 1 steps), the
+    workspace sized for the count asked for; exact on integer operands.  The destination is the left N columns of a wider NaN-filled
+    matrix: the columns beside it keep their bits, written or accumulated."""
+    from lr2ppo_amd import ops
+    g = torch.Generator().manual_seed(M + N + K + splits)
+    a, b = _int_mx(M, K, g, dev), _int_mx(N, K, g, dev)
+    want = a.to_float().double() @ b.to_float().double().t()
+    assert torch.equal(want.float().double(), want)                      # integers below 2^24: fp32 holds the product exactly
+    ws = torch.full((splits * M * N,), float("nan"), device=dev)
+    for accumulate in (False, True):
+        big = torch.full((M, N + 128), float("nan"), device=dev)
+        pre = torch.randn(M, N, generator=g).to(dev)
+        if accumulate:
+            big[:, :N] = pre
+        before = big.clone()
+        ops.gemm_mxfp8_wgrad(a, b, big[:, :N], splits=splits, workspace=ws, accumulate=accumulate)
+        expect = (pre.double() + want).float() if accumulate else want.float()
+        assert torch.equal(big[:, :N], expect), f"accumulate={accumulate}"
+        assert torch.equal(big.view(torch.int32)[:, N:], before.view(torch.int32)[:, N:]), f"accumulate={accumulate}: columns beside the destination"
+
+
 def _small_encoder(pre, dev, seed, layers=2):
     from lr2ppo_amd.finetune.features import TEXT_CONFIG, VIT_CONFIG, encoder_args
     from lr2ppo_amd.tencentpretrain.encoders import str2encoder
