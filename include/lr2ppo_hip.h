@@ -24,7 +24,7 @@ extern "C" {
 #define LR2_ERR_SHAPE (-2)  /* shape not supported by the kernel's tiling */
 #define LR2_ERR_LAUNCH (-3) /* HIP launch failure */
 
-#define LR2_ABI_VERSION 20
+#define LR2_ABI_VERSION 21
 int lr2_abi_version(void);
 /* Fills name[0..len) with the HIP device name and returns the CU count (or <0). */
 int lr2_device_info(char* name, int len);
@@ -40,7 +40,7 @@ typedef struct lr2_epilogue {
   void* out;          /* [M, ld_out] fp32 or NULL (then out_hi must be set) */
   void* out_z;        /* [M, ld_z] pre-activation (act == 1) or NULL */
   void* out_hi;       /* bf16 hi plane [M, ld_planes] or NULL: result ALSO/INSTEAD written as split planes */
-  uint64_t out_lo_off; /* elements from the hi plane to the lo plane */
+  uint64_t out_lo_off; /* elements from the hi plane to the lo plane; 0 (ABI 21): ONE bf16 plane, round to nearest even */
   int32_t ld_planes;
   int32_t ld_resid, ld_aux, ld_out, ld_z;
   int32_t act;        /* 0 none, 1 GELU(erf), 2 multiply by GELU'(aux_z) */
@@ -152,6 +152,8 @@ int lr2_split_planes_multi(const lr2_split_chunk* table_dev, int n_chunks, void*
  * Output row r is written at out + (r / group)*group_stride + (r % group)*D (group<=0: dense), which lets the
  * final XiT LayerNorm write straight into the concat buffer of finetune/ppo.py:224.
  * out (fp32) and/or out_hi (bf16 planes, lo plane out_lo_off elements later, same row mapping) receive the result.
+ * out_lo_off == 0 (ABI 21): out_hi is ONE bf16 plane (round to nearest even -- the hi plane of the planes output and nothing else:
+ * 2 bytes written per element), the A operand of lr2_gemm_bf16.
  * mean/rstd (fp32 [rows]) may be NULL when no backward is needed. */
 int lr2_layernorm_fwd(const void* x, const void* gamma, const void* beta, void* out, void* out_hi, uint64_t out_lo_off,
                       void* mean, void* rstd, int rows, int D, float eps, int mode, int group, uint64_t group_stride,
@@ -389,10 +391,32 @@ int lr2_gemm_mxfp8(const void* a_q, const void* a_scales, const void* b_q, const
  * lr2_gemm_mxfp8 writes with out_lo_off = 0 -- q, k, v = the three column blocks of one [rows, 3E] matrix), single-pass bf16 products,
  * fp32 softmax, key mask -10000 * (seg <= 0) after the scale; the context rows leave as fp32 (o_f32 [batch * L, ld_o]) and / or as
  * MX-FP8 (o_q [batch * L, ld_o] bytes + o_scales [batch * L, ld_o / 32]: the A operand of the output projection, no fp32 round trip, no
- * quantise pass).  head_dim 64, L <= 288, inference only (no dropout).  NOT the parity path: lr2_self_attn_fwd stays the default.
- * replaces: tencentpretrain/layers/multi_headed_attn.py:60-74 in that mode. */
+ * quantise pass) and / or (ABI 21) as ONE bf16 plane (o_bf16 [batch * L, ld_o], round to nearest even of the fp32 context: the A
+ * operand of lr2_gemm_bf16).  head_dim 64, L <= 288, inference only (no dropout).  NOT the parity path: lr2_self_attn_fwd stays the
+ * default.
+ * replaces: tencentpretrain/layers/multi_headed_attn.py:60-74 in those modes. */
 int lr2_self_attn_fwd_bf16(const void* q, const void* k, const void* v, int ld, const int64_t* seg, void* o_f32, void* o_q,
-                           void* o_scales, int ld_o, int batch, int heads, int L, int head_dim, float scale, void* stream);
+                           void* o_scales, void* o_bf16, int ld_o, int batch, int heads, int L, int head_dim, float scale, void* stream);
+/* (ABI 21) *persistent = 1 when lr2_self_attn_fwd_bf16 runs a call of this shape as persistent workgroups (at least one (sequence,
+ * head) pair per CU), 0 for one workgroup per pair.  A test hook of this library's own scheduling; no reference counterpart. */
+int lr2_self_attn_fwd_bf16_plan(int batch, int heads, int L, int ld, int* persistent);
+
+/* ABI 21.  Single-pass bf16 product, the "bf16" inference mode (BASELINE.json configs[2]; FeatureExtractor(precision="bf16")):
+ * C[M, N] = A[M, K] . B[N, K]^T with A and B ONE bf16 plane each (row strides lda / ldb elements, a_bytes / b_bytes addressable from
+ * each pointer: rows past the end read as zero), one v_mfma_f32_16x16x32_bf16 product per tile pair, fp32 accumulate.  NOT the parity
+ * path: an operand keeps 8 mantissa bits.  Epilogue: alpha, bias, act 0 / 1 (GELU), resid; the result goes to out (fp32) and / or
+ * out_hi -- hi / lo planes, or ONE bf16 plane (round to nearest even) when out_lo_off == 0, the convention of lr2_gemm_mxfp8.
+ * Inference only: dropout, act 2, accumulate, out_z, the fused optimizer step and column sums are LR2_ERR_ARG.
+ * K % 64 == 0, lda / ldb % 8 == 0, N % 4 == 0 (else LR2_ERR_SHAPE); M and N may be ragged.
+ * block_m == 256: the 256 x 256 single-pass ping-pong kernel (csrc/gemm256_b1.hip) at ANY M (large products follow
+ * lr2_gemm_row_split_plan as lr2_gemm does); 128 / 64: the general kernel family at passes = 1.
+ * replaces: nn.Linear forward (tencentpretrain/layers/position_ffn.py:12-15, multi_headed_attn.py:55-76) in that mode. */
+int lr2_gemm_bf16(const void* A, const void* B, int M, int N, int K, int lda, int ldb, uint64_t a_bytes, uint64_t b_bytes,
+                  const lr2_epilogue* epi, int block_m, void* stream);
+/* Diagnostic: launches issued by lr2_gemm_bf16 since the library was loaded -- counts[0] the 256 x 256 single-pass kernel, counts[1]
+ * the general kernel family (no device call).  Plain host counters, as lr2_gemm_launch_counts': not synchronised -- meaningful when one
+ * thread issues the launches, which is how tests read them. */
+int lr2_gemm_bf16_launch_counts(uint64_t counts[2]);
 
 /* ABI 20.  MX-FP8 encoder training (FeatureExtractor(precision="mxfp8_train")): the backward's operands, blocked along the axis its
  * products reduce over, and a K-sliced weight-gradient product.

@@ -577,6 +577,7 @@ Epilogue to_device_epilogue(const lr2_epilogue* e) {
 
 int launch_gemm256_nt(const GemmParams& p, hipStream_t stream);   // gemm256.hip
 int launch_gemm256_tn(const GemmParams& p, int splits, hipStream_t stream);
+int launch_gemm256_b1(const GemmParams& p, hipStream_t stream);   // gemm256_b1.hip
 
 }  // namespace lr2gemm
 using namespace lr2gemm;
@@ -730,4 +731,65 @@ extern "C" int lr2_gemm(const void* A, const void* B, int M, int N, int K, int l
     return lr2_colsum(A, a_planes, a_planes ? a_lo_off / 2 : 0, K, M, lda, epi->colsum_ws, K < 128 ? K : 128, epi->colsum, stream);
   }
   return 0;
+}
+
+// ---- single-pass bf16 products of ONE plane per operand (the "bf16" inference mode) -------------------------------------------
+static uint64_t g_launches_b1[2] = {0, 0};     // the 256 x 256 single-pass kernel, the general family at passes = 1
+extern "C" int lr2_gemm_bf16_launch_counts(uint64_t counts[2]) {
+  if (!counts) return LR2_ERR_ARG;
+  counts[0] = g_launches_b1[0];
+  counts[1] = g_launches_b1[1];
+  return 0;
+}
+
+extern "C" int lr2_gemm_bf16(const void* A, const void* B, int M, int N, int K, int lda, int ldb, uint64_t a_bytes, uint64_t b_bytes,
+                             const lr2_epilogue* epi, int block_m, void* stream) {
+  if (!A || !B || M <= 0 || N <= 0 || K <= 0 || !epi || (!epi->out && !epi->out_hi)) return LR2_ERR_ARG;
+  // inference only: no dropout, no GELU', no accumulate, no kept pre-activation, no fused optimizer, no column sums
+  if (epi->drop_p > 0.f || epi->act < 0 || epi->act > 1 || epi->accumulate || epi->out_z || epi->adam_p || epi->colsum) return LR2_ERR_ARG;
+  if (K % 64) return LR2_ERR_SHAPE;             // whole 64-deep K steps on the 256 x 256 kernel AND on the 128- / 64-row family
+  if ((lda % 8) || (ldb % 8) || (N % 4)) return LR2_ERR_SHAPE;
+  if ((epi->out && epi->ld_out % 4) || (epi->resid && epi->ld_resid % 4) || (epi->out_hi && epi->ld_planes % 4)) return LR2_ERR_SHAPE;
+  if (a_bytes >= (1ull << 32) || b_bytes >= (1ull << 32)) return LR2_ERR_SHAPE;
+  const bool use256 = block_m == 256 && a_bytes <= 0xFFFFFD00ull && b_bytes <= 0xFFFFFD00ull;
+  if (block_m != 64) block_m = 128;
+  GemmParams p{};
+  p.A = A;
+  p.B = B;
+  p.M = M;
+  p.N = N;
+  p.K = K;
+  p.lda = lda;
+  p.ldb = ldb;
+  p.a_bytes = (uint32_t)a_bytes;
+  p.b_bytes = (uint32_t)b_bytes;
+  p.k_tiles_per_split = K / 64;
+  p.epi = to_device_epilogue(epi);
+  p.epi.store_nt = (uint64_t)M * (uint64_t)N * (epi->out ? 4ull : 2ull) >= (256ull << 20) ? 1 : 0;   // lr2_gemm's rule, on the bytes written
+  hipStream_t s = (hipStream_t)stream;
+  if (!use256) {
+    ++g_launches_b1[1];
+    return dispatch_form<true, true>(p, 1, block_m, 1, 0, 0, s);
+  }
+  // the row split of lr2_gemm (lr2_gemm_row_split_plan): whole rounds of the chip on the 256 x 256 kernel, the rest on short tiles
+  int M1 = 0, bm2 = 128;
+  if (lr2_gemm_row_split_plan(M, N, K, &M1, &bm2) == 0 && M1 > 0) {
+    GemmParams p1 = p;
+    p1.M = M1;
+    const int rc = launch_gemm256_b1(p1, s);
+    if (rc) return rc;
+    ++g_launches_b1[0];
+    ++g_launches_b1[1];
+    GemmParams p2 = p;
+    p2.M = M - M1;
+    p2.A = (const char*)A + (size_t)M1 * (size_t)lda * 2u;
+    p2.a_bytes = (uint32_t)(a_bytes - (uint64_t)M1 * (uint64_t)lda * 2u);
+    Epilogue& e2 = p2.epi;
+    if (e2.resid) e2.resid += (size_t)M1 * e2.ld_resid;
+    if (e2.out) e2.out += (size_t)M1 * e2.ld_out;
+    if (e2.out_hi) e2.out_hi += (size_t)M1 * e2.ld_planes;
+    return dispatch_form<true, true>(p2, 1, bm2, 1, 0, 0, s);
+  }
+  ++g_launches_b1[0];
+  return launch_gemm256_b1(p, s);
 }

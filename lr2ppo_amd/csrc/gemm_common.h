@@ -163,12 +163,13 @@ const float adam_lr = e.lr_dev ? scalar_load_f32((const float*)e.dev_scalar) : e
     u32x2_t hv, lv;
     split4(v, hv, lv);
     bf16_t* ph = e.out_hi + (size_t)m * e.ld_planes + n;
+    // lo_off == 0: ONE bf16 plane (hi == the value rounded to nearest even) -- lr2_gemm_bf16's operand format; no lo store
     if (e.store_nt) {
       __builtin_nontemporal_store(hv, reinterpret_cast<u32x2_t*>(ph));
-      __builtin_nontemporal_store(lv, reinterpret_cast<u32x2_t*>(ph + e.lo_off));
+      if (e.lo_off) __builtin_nontemporal_store(lv, reinterpret_cast<u32x2_t*>(ph + e.lo_off));
     } else {
       *reinterpret_cast<u32x2_t*>(ph) = hv;
-      *reinterpret_cast<u32x2_t*>(ph + e.lo_off) = lv;
+      if (e.lo_off) *reinterpret_cast<u32x2_t*>(ph + e.lo_off) = lv;
     }
   }
 }
@@ -256,7 +257,8 @@ __device__ __forceinline__ void epilogue_to_slab(f32x4_t (&acc)[MI][NI], float* 
 // Same operations in the same order per element as epilogue_apply4: same bits (tools/dbg/epi_ab.py compares two builds).
 //   ACT 0 / 1 (GELU; Z: store the pre-activation) / 2 (multiply by GELU'(aux));  DROP: mask after the activation;
 //   RESID: add the residual row;  OUT: fp32 result;  PL: bf16 hi / lo planes result;  NT: non-temporal stores.
-template <int NP, int RPP, int NS, int ACT, bool Z, bool DROP, bool RESID, bool OUT, bool PL, bool NT>
+//   LO (with PL): the lo plane is stored too; false = ONE bf16 plane (Epilogue::lo_off == 0, the single-pass bf16 mode).
+template <int NP, int RPP, int NS, int ACT, bool Z, bool DROP, bool RESID, bool OUT, bool PL, bool NT, bool LO = true>
 __device__ __forceinline__ void epilogue_fast(const Epilogue& e, const float4 (&v)[NP], float4 b, const EpiLoads<NS> (&L)[NP],
                                               int m0, int n, int N) {
 #pragma clang fp contract(off)
@@ -293,10 +295,10 @@ __device__ __forceinline__ void epilogue_fast(const Epilogue& e, const float4 (&
       bf16_t* p = e.out_hi + (size_t)m * e.ld_planes + n;
       if constexpr (NT) {
         __builtin_nontemporal_store(hv, reinterpret_cast<u32x2_t*>(p));
-        __builtin_nontemporal_store(lv, reinterpret_cast<u32x2_t*>(p + e.lo_off));
+        if constexpr (LO) __builtin_nontemporal_store(lv, reinterpret_cast<u32x2_t*>(p + e.lo_off));
       } else {
         *reinterpret_cast<u32x2_t*>(p) = hv;
-        *reinterpret_cast<u32x2_t*>(p + e.lo_off) = lv;
+        if constexpr (LO) *reinterpret_cast<u32x2_t*>(p + e.lo_off) = lv;
       }
     }
   }
@@ -304,7 +306,8 @@ __device__ __forceinline__ void epilogue_fast(const Epilogue& e, const float4 (&
 
 // -> true when one of the instantiated forms took the slab.  WIDE 2: the full list (the 256 x 256 kernels, where the encoders'
 // training products run); 1: the 8-wave kernels (the heads' M = 12 544 products); 0: the other planes x planes kernels of the general
-// family, the inference forms only; -1: none (fifty kernel instantiations: compile time).
+// family, the inference forms only; -1: none (fifty kernel instantiations: compile time); 3: the single-pass bf16 kernel
+// (gemm256_b1.hip): the inference forms with ONE bf16 plane or hi / lo planes.
 template <int NP, int RPP, int NS, int WIDE>
 __device__ __forceinline__ bool epilogue_fast_dispatch(const Epilogue& e, const float4 (&v)[NP], float4 b,
                                                        const EpiLoads<NS> (&L)[NP], int m0, int n, int N) {
@@ -314,6 +317,23 @@ __device__ __forceinline__ bool epilogue_fast_dispatch(const Epilogue& e, const 
   const bool z = e.out_z != nullptr, drop = e.drop_scale != 0.0f, resid = e.resid != nullptr, out = e.out != nullptr,
              pl = e.out_hi != nullptr;
   if (z && act != 1) return false;
+  const bool one_plane = pl && e.lo_off == 0;
+  if constexpr (WIDE == 3) {
+    if (z || drop || act > 1) return false;
+#define LR2_FAST1(ACT, RESID, OUT, PL, LO)                                                                             \
+  if (act == ACT && resid == RESID && out == OUT && pl == PL && one_plane == (PL && !LO)) {                           \
+    if (e.store_nt) epilogue_fast<NP, RPP, NS, ACT, false, false, RESID, OUT, PL, true, LO>(e, v, b, L, m0, n, N);    \
+    else epilogue_fast<NP, RPP, NS, ACT, false, false, RESID, OUT, PL, false, LO>(e, v, b, L, m0, n, N);               \
+    return true;                                                                                                     \
+  }
+    LR2_FAST1(0, false, false, true, false)     // bias -> one plane (QKV)
+    LR2_FAST1(1, false, false, true, false)     // bias, GELU -> one plane (FFN-1)
+    LR2_FAST1(0, true, true, false, true)       // bias + residual -> fp32 (attention output, FFN-2)
+    LR2_FAST1(0, false, false, true, true)      // bias -> hi / lo planes (QKV in front of the 3-pass attention kernels)
+#undef LR2_FAST1
+    return false;
+  }
+  if (one_plane) return false;                  // the general path stores the single plane
 #define LR2_FAST(ACT, Z, DROP, RESID, OUT, PL)                                                                         \
   if (act == ACT && z == Z && drop == DROP && resid == RESID && out == OUT && pl == PL) {                             \
     if (e.store_nt) epilogue_fast<NP, RPP, NS, ACT, Z, DROP, RESID, OUT, PL, true>(e, v, b, L, m0, n, N);             \

@@ -65,7 +65,10 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
       y.z = (v[i].z - mean) * rstd * g.z + b.z;
       y.w = (v[i].w - mean) * rstd * g.w + b.w;
       if (out) *reinterpret_cast<float4*>(out + off + e) = y;
-      if (out_hi) store_planes4(out_hi + off + e, out_lo_off, y);
+      if (out_hi) {                             // out_lo_off == 0: ONE bf16 plane (the hi plane and nothing else: 2 B per element)
+        if (out_lo_off) store_planes4(out_hi + off + e, out_lo_off, y);
+        else store_bf16x4(out_hi + off + e, y);
+      }
       if (out_q) {
         // MX-FP8 (csrc/fp8.hip's rule): a 32-column block = 8 consecutive lanes x 4 columns; D % 32 == 0, so a block's lanes are
         // all inside the row or all outside

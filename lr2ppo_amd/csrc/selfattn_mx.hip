@@ -37,8 +37,8 @@ template <int NT, int NW>
 __global__ __launch_bounds__(64 * NW) void self_attn_bf16_mx_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
                                                                     const bf16_t* __restrict__ V, int ld,
                                                                     const int64_t* __restrict__ seg, float* __restrict__ Of,
-                                                                    uint8_t* __restrict__ Oq, uint8_t* __restrict__ Os, int ld_o,
-                                                                    int heads, int L, float scale) {
+                                                                    uint8_t* __restrict__ Oq, uint8_t* __restrict__ Os,
+                                                                    bf16_t* __restrict__ Ob, int ld_o, int heads, int L, float scale) {
   constexpr int LP = 16 * NT;
   constexpr int PLANE = LP * ROW_B;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -173,6 +173,7 @@ __global__ __launch_bounds__(64 * NW) void self_attn_bf16_mx_kernel(const bf16_t
       const float4 v = *reinterpret_cast<const float4*>(slab + r * (HD + 4) + c);
       const size_t row = row0 + (ok ? qr : 0);
       if (Of && ok) *reinterpret_cast<float4*>(Of + row * (size_t)ld_o + col0 + c) = v;
+      if (Ob && ok) store_bf16x4(Ob + row * (size_t)ld_o + col0 + c, v);       // ONE bf16 plane: RNE of the fp32 context
       if (Oq) {
         // the row's 32-column MX block = 8 consecutive lanes x 4 columns (the head's 64 columns are two blocks): as lr2_quant_mxfp8
         float amax = fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
@@ -286,7 +287,7 @@ __device__ __forceinline__ void mx_phase_a(const char* sK, const float* sMask, c
 template <int NT>
 __device__ __forceinline__ void mx_phase_b(const char* sV, float* slab, const bf16x8_t (&pf)[NT / 2], float inv, int sub, int lane, int L,
                                            size_t row0, int col0, float* __restrict__ Of, uint8_t* __restrict__ Oq,
-                                           uint8_t* __restrict__ Os, int ld_o) {
+                                           uint8_t* __restrict__ Os, bf16_t* __restrict__ Ob, int ld_o) {
   const int qn = lane & 15, g = lane >> 4;
   const int i16 = lane & 15, tq = i16 >> 2, tp = i16 & 3;
   uint32_t vb[4];
@@ -325,6 +326,7 @@ __device__ __forceinline__ void mx_phase_b(const char* sV, float* slab, const bf
     const uint32_t lrow = (uint32_t)(ok ? qr : 0);
     const size_t ubase = row0 * (size_t)ld_o + col0, sbase = row0 * (size_t)(ld_o / 32) + (col0 >> 5);
     if (Of && ok) *reinterpret_cast<float4*>(Of + ubase + (lrow * (uint32_t)ld_o + (uint32_t)c)) = v;
+    if (Ob && ok) store_bf16x4(Ob + ubase + (lrow * (uint32_t)ld_o + (uint32_t)c), v);
     if (Oq) {
       float amax = fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
       amax = group8_max(amax);
@@ -351,7 +353,8 @@ __global__ __launch_bounds__(64 * PM_WAVES) void self_attn_bf16_mx_persist_kerne
                                                                                   const bf16_t* __restrict__ V, int ld,
                                                                                   const int64_t* __restrict__ seg, float* __restrict__ Of,
                                                                                   uint8_t* __restrict__ Oq, uint8_t* __restrict__ Os,
-                                                                                  int ld_o, int heads, int L, float scale, int n_pairs,
+                                                                                  bf16_t* __restrict__ Ob, int ld_o, int heads, int L,
+                                                                                  float scale, int n_pairs,
                                                                                   uint32_t kv_bytes) {
   constexpr int LP = 16 * NT;
   constexpr int PLANE = LP * ROW_B;
@@ -445,9 +448,9 @@ __global__ __launch_bounds__(64 * PM_WAVES) void self_attn_bf16_mx_persist_kerne
     const bool more = pn < n_pairs;
     const int bn = __builtin_amdgcn_readfirstlane(pn / heads), hn = pn - bn * heads;
     const size_t row0n = (size_t)bn * L;
-    if (has0) mx_phase_b<NT>(sV, slab, p0, inv0, sub0, mx_opaque(lane), L, row0, col0, Of, Oq, Os, ld_o);
+    if (has0) mx_phase_b<NT>(sV, slab, p0, inv0, sub0, mx_opaque(lane), L, row0, col0, Of, Oq, Os, Ob, ld_o);
     if (more) load_q(row0n, hn * HD, sub0, q0);    // the next pair's first sub-tile: under the second sub-tile's P V
-    if (has1) mx_phase_b<NT>(sV, slab, p1, inv1, sub1, mx_opaque(lane), L, row0, col0, Of, Oq, Os, ld_o);
+    if (has1) mx_phase_b<NT>(sV, slab, p1, inv1, sub1, mx_opaque(lane), L, row0, col0, Of, Oq, Os, Ob, ld_o);
     if (!more) break;
     mx_phase_barrier();
     p = pn; row0 = row0n; col0 = hn * HD;
@@ -464,9 +467,15 @@ static int mx_cu_count() {
   return n;
 }
 
+// the persistent form: at least one pair per CU, 32-bit byte offsets
+static bool takes_persistent(int batch, int heads, int L, int ld) {
+  const uint64_t span = ((uint64_t)batch * L - 1) * (uint64_t)ld * 2u + (uint64_t)heads * HD * 2u;
+  return batch * heads >= mx_cu_count() && (L + 15) / 16 <= 2 * PM_COMPUTE && span < 0xFFFFFF00ull;
+}
+
 template <int NT>
 int launch_persist(const bf16_t* q, const bf16_t* k, const bf16_t* v, int ld, const int64_t* seg, float* of, uint8_t* oq, uint8_t* os,
-                   int ld_o, int batch, int heads, int L, float scale, uint32_t kv_bytes, hipStream_t stream) {
+                   bf16_t* ob, int ld_o, int batch, int heads, int L, float scale, uint32_t kv_bytes, hipStream_t stream) {
   constexpr int LP = 16 * NT;
   const size_t lds = (size_t)2 * LP * ROW_B + (size_t)2 * LP * 4 + (size_t)PM_COMPUTE * 16 * (HD + 4) * 4;
   static bool done = false;
@@ -476,19 +485,17 @@ int launch_persist(const bf16_t* q, const bf16_t* k, const bf16_t* v, int ld, co
   }
   const int n_pairs = batch * heads;
   const int grid = n_pairs < mx_cu_count() ? n_pairs : mx_cu_count();
-  LR2_LAUNCH((self_attn_bf16_mx_persist_kernel<NT>), dim3(grid), dim3(64 * PM_WAVES), lds, stream, q, k, v, ld, seg, of, oq, os, ld_o,
-             heads, L, scale, n_pairs, kv_bytes);
+  LR2_LAUNCH((self_attn_bf16_mx_persist_kernel<NT>), dim3(grid), dim3(64 * PM_WAVES), lds, stream, q, k, v, ld, seg, of, oq, os, ob,
+             ld_o, heads, L, scale, n_pairs, kv_bytes);
   return lr2_launch_status("lr2_self_attn_fwd_bf16(persistent)");
 }
 
 template <int NT>
-int launch(const bf16_t* q, const bf16_t* k, const bf16_t* v, int ld, const int64_t* seg, float* of, uint8_t* oq, uint8_t* os, int ld_o,
-           int batch, int heads, int L, float scale, hipStream_t stream) {
-  {
-    // the persistent form: at least one pair per CU, 32-bit byte offsets
+int launch(const bf16_t* q, const bf16_t* k, const bf16_t* v, int ld, const int64_t* seg, float* of, uint8_t* oq, uint8_t* os, bf16_t* ob,
+           int ld_o, int batch, int heads, int L, float scale, hipStream_t stream) {
+  if (takes_persistent(batch, heads, L, ld)) {
     const uint64_t span = ((uint64_t)batch * L - 1) * (uint64_t)ld * 2u + (uint64_t)heads * HD * 2u;
-    if (batch * heads >= mx_cu_count() && (L + 15) / 16 <= 2 * PM_COMPUTE && span < 0xFFFFFF00ull)
-      return launch_persist<NT>(q, k, v, ld, seg, of, oq, os, ld_o, batch, heads, L, scale, (uint32_t)span, stream);
+    return launch_persist<NT>(q, k, v, ld, seg, of, oq, os, ob, ld_o, batch, heads, L, scale, (uint32_t)span, stream);
   }
   constexpr int LP = 16 * NT, NW = 8;
   const size_t lds = (size_t)2 * LP * ROW_B + (size_t)LP * 4 + (size_t)NW * 16 * (HD + 4) * 4;
@@ -497,21 +504,28 @@ int launch(const bf16_t* q, const bf16_t* k, const bf16_t* v, int ld, const int6
     if (lr2_allow_dynamic_lds(self_attn_bf16_mx_kernel<NT, NW>, lds, "self_attn_fwd_bf16")) return LR2_ERR_LAUNCH;
     done = true;
   }
-  LR2_LAUNCH((self_attn_bf16_mx_kernel<NT, NW>), dim3(1, heads, batch), dim3(64 * NW), lds, stream, q, k, v, ld, seg, of, oq, os, ld_o,
-             heads, L, scale);
+  LR2_LAUNCH((self_attn_bf16_mx_kernel<NT, NW>), dim3(1, heads, batch), dim3(64 * NW), lds, stream, q, k, v, ld, seg, of, oq, os, ob,
+             ld_o, heads, L, scale);
   return lr2_launch_status("lr2_self_attn_fwd_bf16");
 }
 
 }  // namespace
 
+extern "C" int lr2_self_attn_fwd_bf16_plan(int batch, int heads, int L, int ld, int* persistent) {
+  if (!persistent || batch <= 0 || heads <= 0 || L <= 0 || L > 288 || ld <= 0) return LR2_ERR_ARG;
+  *persistent = takes_persistent(batch, heads, L, ld) ? 1 : 0;
+  return 0;
+}
+
 extern "C" int lr2_self_attn_fwd_bf16(const void* q, const void* k, const void* v, int ld, const int64_t* seg, void* o_f32, void* o_q,
-                                      void* o_scales, int ld_o, int batch, int heads, int L, int head_dim, float scale, void* stream) {
-  if (!q || !k || !v || !seg || (!o_f32 && !o_q) || batch <= 0 || heads <= 0 || L <= 0) return LR2_ERR_ARG;
+                                      void* o_scales, void* o_bf16, int ld_o, int batch, int heads, int L, int head_dim, float scale,
+                                      void* stream) {
+  if (!q || !k || !v || !seg || (!o_f32 && !o_q && !o_bf16) || batch <= 0 || heads <= 0 || L <= 0) return LR2_ERR_ARG;
   if ((o_q != nullptr) != (o_scales != nullptr)) return LR2_ERR_ARG;
   if (head_dim != HD || L > 288 || (ld % 8) || ld_o < heads * HD || (ld_o % 32)) return LR2_ERR_SHAPE;
   const bf16_t *qq = (const bf16_t*)q, *kk = (const bf16_t*)k, *vv = (const bf16_t*)v;
   hipStream_t s = (hipStream_t)stream;
-#define GO(NT) return launch<NT>(qq, kk, vv, ld, seg, (float*)o_f32, (uint8_t*)o_q, (uint8_t*)o_scales, ld_o, batch, heads, L, scale, s)
+#define GO(NT) return launch<NT>(qq, kk, vv, ld, seg, (float*)o_f32, (uint8_t*)o_q, (uint8_t*)o_scales, (bf16_t*)o_bf16, ld_o, batch, heads, L, scale, s)
   if (L <= 64) GO(4);
   if (L <= 128) GO(8);
   if (L <= 224) GO(14);

@@ -155,12 +155,16 @@ class FeatureExtractor(nn.Module):
     precision: "split_bf16" (default: the fp32-grade parity path) or "mxfp8" -- extract() / no-grad forward() run every
     projection of both stacks as an MX-FP8 product (TransformerEncoder.forward_fp8); training paths refuse that mode -- or
     "mxfp8_train": fine-tuning in MX-FP8, every projection's forward, input gradient and weight gradient an MX-FP8 product
-    (TransformerEncoder._forward_train_fp8 / _backward_train_fp8) on every route, extract() included (that forward, dropout off).
+    (TransformerEncoder._forward_train_fp8 / _backward_train_fp8) on every route, extract() included (that forward, dropout off) --
+    or "bf16" (BASELINE.json configs[2]'s literal dtype): extract() / no-grad forward() run every projection and the attention
+    of both stacks as ONE bf16 pass over single-plane activations (TransformerEncoder.forward_bf16); inference only, like "mxfp8",
+    ten times closer to the parity path than it.
     recompute: the training forwards of both towers keep each layer's input only and the backward re-runs a layer's forward right
     before that layer's backward (TransformerEncoder.recompute): the same bits, ~1/12 of the activation memory, one more
     forward per step.  Embeddings, the projection and the heads keep their activations."""
 
-    PRECISIONS = ("split_bf16", "mxfp8", "mxfp8_train")
+    PRECISIONS = ("split_bf16", "mxfp8", "mxfp8_train", "bf16")
+    INFERENCE_ONLY = ("mxfp8", "bf16")
 
     def __init__(self, vit_args: Optional[argparse.Namespace] = None, text_args: Optional[argparse.Namespace] = None,
                  vocab_size: int = ROBERTA_VOCAB, seq_length: int = 196, feat_dim: Optional[int] = None,
@@ -175,8 +179,8 @@ class FeatureExtractor(nn.Module):
                              f"heads' feature width {self.feat_dim}, got {self.text_args.hidden_size}")
         if precision not in self.PRECISIONS:
             raise ValueError(f"precision must be one of {self.PRECISIONS}")
-        if recompute and precision == "mxfp8":
-            raise ValueError("recompute trades time for memory in the TRAINING schedules; precision='mxfp8' is inference only")
+        if recompute and precision in self.INFERENCE_ONLY:
+            raise ValueError(f"recompute trades time for memory in the TRAINING schedules; precision='{precision}' is inference only")
         self.precision, self.recompute = precision, bool(recompute)
         self.image = EncoderStack(self.vit_args, vocab_size)
         self.text = EncoderStack(self.text_args, vocab_size)
@@ -216,8 +220,9 @@ class FeatureExtractor(nn.Module):
         seg = torch.ones(B * n_img, L, dtype=torch.int64, device=frames.device)
         # pooling(h, seg, "first") of utils/misc.py:23-35 = (h * seg)[:, 0, :]: only token 0 of the encoder output is consumed,
         # so the last layer is evaluated for that token only (inference; bit-for-bit the full schedule's kernels on B rows)
-        if self._fp8_now():
-            h0 = self.image.encoder.forward_fp8(self.image.embedding(flat, seg), seg, first_only=True)
+        fast = self._fast_now()
+        if fast:
+            h0 = getattr(self.image.encoder, fast)(self.image.embedding(flat, seg), seg, first_only=True)
         else:
             h0 = self.image.forward_first_token(flat, seg)
         h0 = h0 * seg[:, :1].type_as(h0)
@@ -225,14 +230,16 @@ class FeatureExtractor(nn.Module):
             h0 = self.visual_projection(h0)
         return h0.reshape(B, n_img, -1)
 
-    def _fp8_now(self) -> bool:
-        """True when this call takes the MX-FP8 route: precision "mxfp8" and nothing asks for gradients or dropout."""
-        if self.precision != "mxfp8":
-            return False
+    def _fast_now(self) -> Optional[str]:
+        """The encoder method this call takes in an inference-only precision ("forward_fp8" for "mxfp8", "forward_bf16" for "bf16"),
+        None on the other precisions; raises when something asks for gradients or dropout."""
+        if self.precision not in self.INFERENCE_ONLY:
+            return None
         if self.training or (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())):
-            raise NotImplementedError("FeatureExtractor(precision='mxfp8') is an inference mode (frozen feature extraction: "
-                                      "extract(), or eval() under torch.no_grad()); train the encoders in 'split_bf16'")
-        return True
+            raise NotImplementedError(f"FeatureExtractor(precision='{self.precision}') is an inference mode (frozen feature "
+                                      "extraction: extract(), or eval() under torch.no_grad()); train the encoders in "
+                                      "'split_bf16' or 'mxfp8_train'")
+        return "forward_fp8" if self.precision == "mxfp8" else "forward_bf16"
 
     def text_features(self, ids: torch.Tensor, seg: Optional[torch.Tensor] = None) -> torch.Tensor:
         """ids [B, T, L] int64 (+ seg [B, T, L]; default all ones) -> text_emb [B, T, L, hidden]."""
@@ -242,8 +249,9 @@ class FeatureExtractor(nn.Module):
         if seg is None:
             seg = torch.ones_like(ids)
         ids2, seg2 = ids.reshape(B * T, L), seg.reshape(B * T, L)
-        if self._fp8_now():
-            h = self.text.encoder.forward_fp8(self.text.embedding(ids2, seg2), seg2)
+        fast = self._fast_now()
+        if fast:
+            h = getattr(self.text.encoder, fast)(self.text.embedding(ids2, seg2), seg2)
         else:
             h = self.text(ids2, seg2)
         return h.reshape(B, T, L, -1)
@@ -294,9 +302,9 @@ class FeatureExtractor(nn.Module):
         multi_headed_attn.py:68); ctx goes to backward_train."""
         if not frames.is_cuda or not ids.is_cuda:
             raise TypeError("lr2ppo_amd: frames / ids must live on the HIP device (no CPU path)")
-        if self.precision == "mxfp8":
-            raise NotImplementedError("forward_train: the encoders train in 'split_bf16' or 'mxfp8_train' (precision='mxfp8' is "
-                                      "inference only)")
+        if self.precision in self.INFERENCE_ONLY:
+            raise NotImplementedError(f"forward_train: the encoders train in 'split_bf16' or 'mxfp8_train' (precision="
+                                      f"'{self.precision}' is inference only)")
         B, n_img = frames.shape[:2]
         T, L = ids.shape[1:]
         if L != self.seq_length:
@@ -428,6 +436,9 @@ def raw_input_opts(parser):
     parser.add_argument("--fp8_features", action="store_true",
                         help="with --raw_inputs and frozen encoders: every projection of both stacks as an MX-FP8 product on the "
                              "block-scaled MFMA (FeatureExtractor(precision='mxfp8'); a few per cent from the default features)")
+    parser.add_argument("--bf16_features", action="store_true",
+                        help="with --raw_inputs and frozen encoders: every projection and the attention of both stacks as ONE bf16 "
+                             "pass (FeatureExtractor(precision='bf16'); features within ~1e-2 of the default ones)")
     parser.add_argument("--fp8_finetune", action="store_true",
                         help="with --raw_inputs --finetune_encoders: train both stacks with MX-FP8 products forward and backward "
                              "(FeatureExtractor(precision='mxfp8_train'))")
@@ -446,12 +457,16 @@ def build_extractor(args, num_tasks: int = 1, trainable: bool = False) -> Featur
     if fp8 and trainable:
         raise ValueError("--fp8_features is for frozen feature extraction; drop it or --finetune_encoders")
     fp8_train = bool(getattr(args, "fp8_finetune", False))
+    bf16 = bool(getattr(args, "bf16_features", False))
+    if bf16 and (fp8 or trainable or fp8_train):
+        raise ValueError("--bf16_features is for frozen feature extraction in one bf16 pass: it excludes --fp8_features, "
+                         "--finetune_encoders and --fp8_finetune")
     if fp8_train and not trainable:
         raise ValueError("--fp8_finetune trains the encoders in MX-FP8: it needs --finetune_encoders")
     recompute = bool(getattr(args, "recompute_activations", False))
     if recompute and not trainable:
         raise ValueError("--recompute_activations is a training-memory switch: it needs --finetune_encoders")
-    precision = "mxfp8" if fp8 else ("mxfp8_train" if fp8_train else "split_bf16")
+    precision = "mxfp8" if fp8 else ("bf16" if bf16 else ("mxfp8_train" if fp8_train else "split_bf16"))
     fx = FeatureExtractor(encoder_args(IMAGE_TOWERS.get(tower, tower), **over), encoder_args(TEXT_CONFIG, **over),
                           seq_length=args.seq_length, feat_dim=args.visual_feat_dim, precision=precision,
                           recompute=recompute)

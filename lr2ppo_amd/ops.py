@@ -424,16 +424,97 @@ def _ld(t: Optional[torch.Tensor], default: int) -> int:
 
 
 def layernorm_fwd(x, gamma, beta, out, mean=None, rstd=None, *, rows, D, eps=1e-5, mode=0, group=0, group_stride=0,
-                  out_planes: Optional[Planes] = None):
-    """out (fp32) and/or out_planes receive LN(x); both use the (group, group_stride) row mapping."""
+                  out_planes: Optional[Planes] = None, out_plane: Optional[torch.Tensor] = None):
+    """out (fp32) and/or out_planes receive LN(x); both use the (group, group_stride) row mapping.
+    out_plane (instead of out_planes): the result as ONE bf16 plane (a 2-byte HIP tensor of rows * D elements, round to nearest
+    even): the A operand of gemm_bf16."""
     _chk_f32(x, gamma, beta, out, mean, rstd)
-    with _Timed(f"lnfwd_R{rows}_D{D}", 0.0, 8.0 * rows * D):
-        rc = _nat.lib().lr2_layernorm_fwd(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(out),
-                                          out_planes.data_ptr() if out_planes is not None else None,
-                                          out_planes.lo_off if out_planes is not None else 0, _ptr(mean), _ptr(rstd), rows, D,
-                                          eps, mode, group, group_stride, _stream())
+    hi, lo_off = (out_planes.data_ptr(), out_planes.lo_off) if out_planes is not None else (None, 0)
+    if out_plane is not None:
+        if out_planes is not None:
+            raise ValueError("layernorm_fwd: out_plane excludes out_planes")
+        hi = _plane_ptr(out_plane, rows * D, "layernorm_fwd: out_plane")
+    with _Timed(f"lnfwd_R{rows}_D{D}", 0.0, (6.0 if out_plane is not None else 8.0) * rows * D):
+        rc = _nat.lib().lr2_layernorm_fwd(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(out), hi, lo_off, _ptr(mean),
+                                          _ptr(rstd), rows, D, eps, mode, group, group_stride, _stream())
     _nat.check(rc, "lr2_layernorm_fwd")
-    return out if out is not None else out_planes
+    return out if out is not None else (out_planes if out_planes is not None else out_plane)
+
+
+def _plane_ptr(t: torch.Tensor, numel: int, what: str) -> int:
+    """data pointer of ONE bf16 plane: a 2-byte HIP tensor (int16 / bfloat16) of at least `numel` elements."""
+    if t.element_size() != 2 or not t.is_cuda or t.numel() < numel:
+        raise TypeError(f"{what} must be a 2-byte HIP tensor of at least {numel} elements")
+    return t.data_ptr()
+
+
+@functools.lru_cache(maxsize=4096)
+def use_gemm256_b1(M: int, N: int, K: int) -> bool:
+    """True when a single-pass bf16 product should run on the 256 x 256 ping-pong kernel (csrc/gemm256_b1.hip) rather than on the
+    128- / 64-row family at passes = 1.  Fitted to tools/gemm_bench.py --bf16 --bm {256,128,64} on MI355X (us; 256 / 128 / 64 rows):
+      M = 100864: N 3072 K 768  752 / 772 / -;  N 768 K 3072  481 / 672 / -;  N 2304 K 768  580 / 678 / -
+      M = 12544:  N 3072 K 768  112 / 130 / -  (588 tiles: row split);  N 768 K 3072  85 / 119 / -  (147 tiles: 192-row tiles);
+                  N 2304 K 768  83 / 102 / 87  (441 tiles);  N 768 K 768  34.8 / 48.6 / 35.0  (147 tiles)
+      M = 6304:   N 2304 K 768  43.8 / 52.5 / 48.2  (225 tiles);  N 3072 K 768  67.9 / 74.1 / 65.4  (300 tiles);
+                  N 768 K 768  32.6 / 25.5 / 20.6  (75 tiles);  N 768 K 3072  75.7 / 61.3 / 52.7  (75 tiles)
+    -> the 256 x 256 kernel from half a round of tiles up, except just over one round (256 < tiles < 384: a second round less than
+    half full, where the 64-row tiles are level or ahead)."""
+    if K % 64:
+        return False
+    tiles = ((M + 255) // 256) * ((N + 255) // 256)
+    return tiles >= 128 and not 256 < tiles < 384
+
+
+def _bf16_fallback_block_m(M: int, N: int) -> int:
+    """Tile height of the general family for a single-pass product the 256 x 256 kernel does not take: 64 rows below three rounds of
+    128-row tiles (choose_tiling's threshold; ahead of 128 rows on every shape measured above), else 128."""
+    return 64 if ((M + 127) // 128) * ((N + 127) // 128) < 1536 else 128
+
+
+def gemm_bf16(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor], M: int, N: int, K: int, *,
+              lda: Optional[int] = None, ldb: Optional[int] = None, ld_out: Optional[int] = None, bias: Optional[torch.Tensor] = None,
+              act: int = 0, resid: Optional[torch.Tensor] = None, alpha: float = 1.0, out_plane: Optional[torch.Tensor] = None,
+              out_planes: Optional[Planes] = None, planes_col: int = 0, block_m: Optional[int] = None):
+    """out[M, N] = a[M, K] @ b[N, K]^T (+ bias) (act 1: GELU) (+ resid) as ONE bf16 pass (lr2_gemm_bf16): a, b are single bf16 planes
+    (2-byte HIP tensors; a Planes matrix contributes its hi plane = bf16(x)).  The result goes to `out` (fp32) and / or ONE bf16
+    plane `out_plane` (round to nearest even) or hi / lo `out_planes`.  Inference only: the bf16 mode, never the parity path.
+    planes_col: the result's N columns go to columns [planes_col, planes_col + N) of a wider `out_planes` matrix [M, >= planes_col + N].
+    block_m: 256 = the 256 x 256 single-pass kernel (any M), 128 / 64 = the general family; None: by size (use_gemm256_b1)."""
+    _chk_f32(out, bias, resid)
+    lda = K if lda is None else lda
+    ldb = K if ldb is None else ldb
+    if isinstance(a, Planes):
+        a = a.buf[:a.rows * a.cols]
+    if isinstance(b, Planes):
+        b = b.buf[:b.rows * b.cols]
+    a_ptr = _plane_ptr(a, (M - 1) * lda + K, "gemm_bf16: a")
+    b_ptr = _plane_ptr(b, (N - 1) * ldb + K, "gemm_bf16: b")
+    if out_plane is not None and out_planes is not None:
+        raise ValueError("gemm_bf16: out_plane excludes out_planes")
+    e = _nat.Epilogue()
+    e.bias, e.resid, e.out = _ptr(bias), _ptr(resid), _ptr(out)
+    e.ld_resid, e.ld_out = _ld(resid, N), (N if ld_out is None else ld_out)
+    if out_plane is not None:
+        e.out_hi, e.out_lo_off, e.ld_planes = _plane_ptr(out_plane, M * N, "gemm_bf16: out_plane"), 0, N
+    elif out_planes is not None:
+        if out_planes.rows != M or planes_col < 0 or planes_col % 4 or planes_col + N > out_planes.cols:
+            raise ValueError("gemm_bf16: out_planes must be [M, >= planes_col + N], planes_col a multiple of 4")
+        e.out_hi, e.out_lo_off, e.ld_planes = out_planes.data_ptr() + 2 * planes_col, out_planes.lo_off, out_planes.cols
+    e.act, e.alpha = act, alpha
+    if block_m is None:
+        block_m = 256 if use_gemm256_b1(M, N, K) else _bf16_fallback_block_m(M, N)
+    with _Timed(f"gemm_bf16_M{M}_N{N}_K{K}", 2.0 * M * N * K, 2.0 * (M * K + N * K) + (4.0 if out is not None else 2.0) * M * N):
+        rc = _nat.lib().lr2_gemm_bf16(a_ptr, b_ptr, M, N, K, lda, ldb, a.numel() * 2, b.numel() * 2, C.byref(e), block_m, _stream())
+    if rc:
+        _nat.check(rc, f"lr2_gemm_bf16(M={M},N={N},K={K},block_m={block_m})")
+    return out if out is not None else (out_plane if out_plane is not None else out_planes)
+
+
+def gemm_bf16_launch_counts():
+    """(launches of the 256 x 256 single-pass kernel, launches of the general family) by gemm_bf16 since the library was loaded."""
+    c = (C.c_uint64 * 2)()
+    _nat.check(_nat.lib().lr2_gemm_bf16_launch_counts(c), "lr2_gemm_bf16_launch_counts")
+    return int(c[0]), int(c[1])
 
 
 # workgroups of the LayerNorm backward (each leaves one partial row of d gamma / d beta): 4 per CU.  With one per CU (round 2) the
@@ -881,26 +962,36 @@ def dropout_residual(y: torch.Tensor, resid: torch.Tensor, out: torch.Tensor, dr
 
 
 def self_attn_fwd_bf16(qkv: torch.Tensor, seg, *, batch, heads, L, head_dim, scale, out: Optional[torch.Tensor] = None,
-                       out_mx: Optional[Mx8] = None):
-    """Encoder self-attention of the MX-FP8 mode (lr2_self_attn_fwd_bf16).  qkv: ONE bf16 plane [batch * L, 3E] = [Q | K | V] (a 2-byte
-    HIP tensor: what gemm_mxfp8(out_bf16=...) writes); the context as fp32 `out` [batch * L, E] and / or as MX-FP8 `out_mx`."""
+                       out_mx: Optional[Mx8] = None, out_plane: Optional[torch.Tensor] = None):
+    """Encoder self-attention of the MX-FP8 and bf16 modes (lr2_self_attn_fwd_bf16).  qkv: ONE bf16 plane [batch * L, 3E] = [Q | K | V]
+    (a 2-byte HIP tensor: what gemm_mxfp8(out_bf16=...) / gemm_bf16(out_plane=...) write); the context as fp32 `out` [batch * L, E]
+    and / or as MX-FP8 `out_mx` and / or as ONE bf16 plane `out_plane` (a 2-byte HIP tensor [batch * L, E])."""
     E = heads * head_dim
     if qkv.element_size() != 2 or not qkv.is_cuda or qkv.numel() < batch * L * 3 * E:
         raise TypeError("self_attn_fwd_bf16: qkv is a 2-byte HIP tensor [batch * L, 3 * heads * head_dim]")
     if seg.dtype != torch.int64:
         raise TypeError("seg must be int64")
     _chk_f32(out)
-    if out is None and out_mx is None:
-        raise ValueError("self_attn_fwd_bf16: out and / or out_mx")
+    if out is None and out_mx is None and out_plane is None:
+        raise ValueError("self_attn_fwd_bf16: out and / or out_mx and / or out_plane")
+    ob = _plane_ptr(out_plane, batch * L * E, "self_attn_fwd_bf16: out_plane") if out_plane is not None else None
     if out_mx is not None and (out_mx.rows != batch * L or out_mx.cols != E):
         raise ValueError("self_attn_fwd_bf16: out_mx must be [batch * L, heads * head_dim]")
     base = qkv.data_ptr()
     with _Timed(f"selfattn_bf16_B{batch}_H{heads}_L{L}", 4.0 * batch * heads * L * L * head_dim, 7.0 * batch * L * E):
         _nat.check(_nat.lib().lr2_self_attn_fwd_bf16(base, base + 2 * E, base + 4 * E, 3 * E, seg.data_ptr(), _ptr(out),
                                                      out_mx.q.data_ptr() if out_mx is not None else None,
-                                                     out_mx.s.data_ptr() if out_mx is not None else None, E, batch, heads, L, head_dim,
-                                                     scale, _stream()), "lr2_self_attn_fwd_bf16")
-    return out if out is not None else out_mx
+                                                     out_mx.s.data_ptr() if out_mx is not None else None, ob, E, batch, heads, L,
+                                                     head_dim, scale, _stream()), "lr2_self_attn_fwd_bf16")
+    return out if out is not None else (out_mx if out_mx is not None else out_plane)
+
+
+def self_attn_bf16_plan(batch: int, heads: int, L: int, ld: Optional[int] = None) -> bool:
+    """True when self_attn_fwd_bf16 runs a call of this shape as persistent workgroups (lr2_self_attn_fwd_bf16_plan)."""
+    f = C.c_int()
+    _nat.check(_nat.lib().lr2_self_attn_fwd_bf16_plan(batch, heads, L, 3 * heads * 64 if ld is None else ld, C.byref(f)),
+               "lr2_self_attn_fwd_bf16_plan")
+    return bool(f.value)
 
 
 def text_embed(src, seg, word, pos, seg_table, out, *, rows, L, D, err: Optional[torch.Tensor] = None):

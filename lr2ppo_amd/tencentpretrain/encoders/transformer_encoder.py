@@ -352,6 +352,98 @@ class TransformerEncoder(nn.Module):
             out.view(M, E).copy_(h)
         return out
 
+    # ---- single-pass bf16 inference (BASELINE.json configs[2] "bf16"): NOT the parity path, the mode between it and MX-FP8 ------
+    # replaces, in that mode, the nn.Linear calls of tencentpretrain/layers/multi_headed_attn.py:55-76 and position_ffn.py:12-15 and the
+    # scores / softmax / context of multi_headed_attn.py:60-74 -- the same sites as forward_fp8.
+    @torch.no_grad()
+    def forward_bf16(self, emb, seg, first_only: bool = False):
+        """forward(emb, seg) with every GEMM operand ONE bf16 plane and every projection ONE bf16 pass (ops.gemm_bf16,
+        csrc/gemm256_b1.hip): the LayerNorm output, Q | K | V as one [M, 3E] plane, the attention context (ops.self_attn_fwd_bf16) and
+        GELU(z) are written as a single plane each by the kernel that produces them; the residual stream stays fp32.  The weights are
+        the hi planes of _weight_planes (hi == bf16(W)): no copy, no cache of their own.  A third of the parity path's matrix work
+        and half its activation traffic; features 4-7e-3 (relative) from forward()'s -- FeatureExtractor(precision="bf16").
+        L > 288: the 3-pass attention kernels (the QKV product then writes hi / lo planes, the context goes through split_planes).
+        Head width below 64 (a multiple of 4): the same kernels, which are built for head width 64, on heads ZERO-PADDED to 64 columns
+        -- one small bf16 product per head and per Q / K / V block writes its columns into a zeroed [M, 3 * heads * 64] planes matrix
+        (zero columns add nothing to Q K^T and give zero context columns); a correct route for small test models, not a fast one.
+        first_only: -> hidden[:, 0, :] ([batch, hidden]): the last layer computes K | V for every row (a bf16 product) and everything
+        behind the scores for row 0 only (forward_first_token's schedule, B rows: split-bf16)."""
+        if emb.dtype != torch.float32 or not emb.is_cuda:
+            raise TypeError("lr2ppo_amd: emb must be a float32 tensor on the HIP device (no CPU path)")
+        B, L, E = emb.shape
+        H, hd, M = self.heads_num, E // self.heads_num, B * L
+        F = self.transformer[0].feed_forward.linear_1.out_features
+        if E % 64 or F % 64:
+            raise ValueError("forward_bf16: hidden and feed-forward widths must be multiples of 64")
+        if hd != 64 and (hd > 64 or hd % 4):
+            raise ValueError("forward_bf16: head width must be 64, or a multiple of 4 below it (zero-padded heads)")
+        if first_only and hd != 64:                                   # lr2_first_token_attn is built for head width 64
+            return self.forward_bf16(emb, seg)[:, 0, :].contiguous()
+        if self._ws is None or self._ws.device != emb.device:
+            self._ws = engine.Workspace(emb.device)
+        ws, dev = self._ws, emb.device
+        seg = seg.to(device=dev, dtype=torch.int64).contiguous().view(-1)
+        W = self._weight_planes(dev)
+        pre = self.layernorm_positioning == "pre"
+        h, h2 = ws.mat("h", M, E), ws.mat("h2", M, E)
+        # the planes buffers of _forward_infer, their first half used as the single plane
+        x_p, qkv_p, o_p = ws.planes("x_p", M, E), ws.planes("qkv_p", M, 3 * E), ws.planes("o_p", M, E)
+        x_b, qkv_b, o_b = x_p.buf[:M * E], qkv_p.buf[:M * 3 * E], o_p.buf[:M * E]
+        t_b, ff_b = ws.planes("t_p", M, E).buf[:M * E], ws.planes("ff_p", M, F).buf[:M * F]
+        fast_attn = hd == 64 and L <= 288
+        h.copy_(emb.contiguous().view(M, E))
+        scale = 1.0 / math.sqrt(float(hd))
+        if not pre:
+            ops.split_planes(h, x_p)                                  # hi plane = bf16(h): the first layer's operand
+        for li, (layer, w) in enumerate(zip(self.transformer, W)):
+            att, ffn, ln1, ln2 = layer.self_attn, layer.feed_forward, layer.layer_norm_1, layer.layer_norm_2
+            if pre:
+                ops.layernorm_fwd(h, ln1.gamma.data, ln1.beta.data, None, rows=M, D=E, eps=ln1.eps, mode=1, out_plane=x_b)
+            if first_only and li == self.layers_num - 1:
+                kv_p = ws.planes("kv_p", M, 2 * E)
+                ops.gemm_bf16(x_b, w["wqkv"].buf[E * E:3 * E * E], None, M, 2 * E, E, bias=w["bqkv"][E:], out_planes=kv_p)
+                return self._last_layer_first_token(ws, layer, w, h, None, seg, B, L, E, F, kv_p=kv_p)
+            if fast_attn:
+                ops.gemm_bf16(x_b, w["wqkv"], None, M, 3 * E, E, bias=w["bqkv"], out_plane=qkv_b)
+                ops.self_attn_fwd_bf16(qkv_b, seg, batch=B, heads=H, L=L, head_dim=hd, scale=scale, out_plane=o_b)
+            elif hd != 64:
+                Ep, o32 = H * 64, ws.mat("bf16_o", M, E)
+                pad_p, pad_o = ws.planes("bf16_qkv_pad", M, 3 * Ep), ws.mat("bf16_o_pad", M, Ep)
+                if li == 0:
+                    pad_p.buf[:2 * M * 3 * Ep].zero_()                 # the padding columns: written by nothing below
+                w_hi = w["wqkv"].buf
+                for blk in range(3):
+                    for hh in range(H):
+                        r0 = blk * E + hh * hd                        # rows of [Wq; Wk; Wv] = this head's output columns
+                        ops.gemm_bf16(x_b, w_hi[r0 * E:(r0 + hd) * E], None, M, hd, E, bias=w["bqkv"][r0:r0 + hd],
+                                      out_planes=pad_p, planes_col=blk * Ep + hh * 64)
+                ops.self_attn_fwd(pad_p, seg, pad_o, batch=B, heads=H, L=L, head_dim=64, scale=scale)
+                o32.copy_(pad_o.view(M, H, 64)[:, :, :hd].reshape(M, E))
+                ops.split_planes(o32, o_p)                            # hi plane = bf16(context)
+            else:
+                o32 = ws.mat("bf16_o", M, E)
+                ops.gemm_bf16(x_b, w["wqkv"], None, M, 3 * E, E, bias=w["bqkv"], out_planes=qkv_p)    # the 3-pass kernels take hi / lo planes
+                ops.self_attn_fwd(qkv_p, seg, o32, batch=B, heads=H, L=L, head_dim=hd, scale=scale)
+                ops.split_planes(o32, o_p)                            # hi plane = bf16(context)
+            ops.gemm_bf16(o_b, w["wo"], h2, M, E, E, bias=att.final_linear.bias.data, resid=h)
+            if pre:                                                   # layers/transformer.py:63-73
+                ops.layernorm_fwd(h2, ln2.gamma.data, ln2.beta.data, None, rows=M, D=E, eps=ln2.eps, mode=1, out_plane=t_b)
+                ops.gemm_bf16(t_b, w["w1"], None, M, F, E, bias=ffn.linear_1.bias.data, act=1, out_plane=ff_b)
+                ops.gemm_bf16(ff_b, w["w2"], h, M, E, F, bias=ffn.linear_2.bias.data, resid=h2)
+            else:                                                     # layers/transformer.py:54-61
+                xn = ws.mat("bf16_xn", M, E)
+                ops.layernorm_fwd(h2, ln1.gamma.data, ln1.beta.data, xn, rows=M, D=E, eps=ln1.eps, mode=1, out_plane=t_b)
+                ops.gemm_bf16(t_b, w["w1"], None, M, F, E, bias=ffn.linear_1.bias.data, act=1, out_plane=ff_b)
+                ops.gemm_bf16(ff_b, w["w2"], h2, M, E, F, bias=ffn.linear_2.bias.data, resid=xn)
+                ops.layernorm_fwd(h2, ln2.gamma.data, ln2.beta.data, h, rows=M, D=E, eps=ln2.eps, mode=1, out_plane=x_b)
+        out = torch.empty(B, L, E, device=dev)
+        if self.final_layernorm:
+            ops.layernorm_fwd(h, self.layer_norm.gamma.data, self.layer_norm.beta.data, out.view(M, E), rows=M, D=E,
+                              eps=self.layer_norm.eps, mode=1)
+        else:
+            out.view(M, E).copy_(h)
+        return out
+
     def _last_layer_first_token(self, ws, layer, w, h, x_p, seg, B, L, E, F, kv_p=None):
         """Last layer of the inference schedule for row 0 of every sequence.  h: the layer's input [B*L, E] (fp32); x_p: the
         planes its QKV projection reads (LayerNorm_1(h) for 'pre', h itself for 'post').  K, V: all rows; everything after the

@@ -33,5 +33,14 @@ echo "== stage 1 on RAW inputs: ViT + RoBERTa stacks (2 layers each here) in fro
 python -m lr2ppo_amd.finetune.pointwise $COMMON --mode reg --max_tags 2 --epochs_num 1 --report_steps 2 --synthetic_items 4 \
   --synthetic_val_items 2 --max_steps 2 --raw_inputs --finetune_encoders --encoder_layers 2 \
   --output_model_path "$OUT/stage1_raw.bin" --log_path "$OUT/stage1_raw.log"
+echo "== the three launchers on RAW inputs with the frozen stacks in ONE bf16 pass (--bf16_features; 2 layers each here)"
+RAW="--raw_inputs --bf16_features --encoder_layers 2 --synthetic_items 4 --synthetic_val_items 2"
+python -m lr2ppo_amd.finetune.pointwise $COMMON --mode reg --max_tags 2 --epochs_num 1 --report_steps 2 --max_steps 2 $RAW \
+  --output_model_path "$OUT/stage1_bf16.bin" --log_path "$OUT/stage1_bf16.log"
+python -m lr2ppo_amd.finetune.reward_pair_dataloader $COMMON --mode cls --epochs_num 1 --report_steps 2 --max_steps 2 $RAW \
+  --output_model_path "$OUT/stage2_bf16.bin" --log_path "$OUT/stage2_bf16.log"
+python -m lr2ppo_amd.finetune.ppo $COMMON --mode reg --epochs_num 2 --critic_learning_rate 1e-4 --max_timesteps 1 \
+  --update_timesteps 2 --kl_div_loss_weight 0.001 --entropy_weight 0.001 --value_clip 0.5 --max_cycles 1 $RAW \
+  --output_model_path "$OUT/stage3_bf16.bin" --log_path "$OUT/stage3_bf16.log"
 ls -la "$OUT"
 echo CLI_SMOKE_OK

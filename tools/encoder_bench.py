@@ -40,12 +40,15 @@ def flops(B, L, E=768, F=3072, layers=12, heads=12, first_token_only=False):
     return (layers - 1) * (gemm + attn) + last
 
 
-def measure_forward(batch_items=32, tags=2, n_img=16, iters=3, passes=3, dev=None):
+def measure_forward(batch_items=32, tags=2, n_img=16, iters=3, passes=3, dev=None, precision="split_bf16"):
     """Dual-encoder forward at the PPO step's feature-extraction shapes: ViT-B/16 over batch_items*n_img frames
     [*, 197, 768], RoBERTa-base over batch_items*tags label sequences [*, 196, 768]; random N(0, 0.02) weights.
-    -> {"ms", "algorithmic_tflop", "tflops", "mfma_issue_frac"} (MFMA issue fraction = passes * flops / time / 2.5 PF)."""
+    -> {"ms", "algorithmic_tflop", "tflops", "mfma_issue_frac"} (MFMA issue fraction = passes * flops / time / 2.5 PF).
+    precision: "split_bf16" (enc.forward), "bf16" (enc.forward_bf16: one pass) or "mxfp8" (enc.forward_fp8)."""
     dev = dev or torch.device("cuda:0")
     ops.set_gemm_passes(passes)
+    if precision != "split_bf16":
+        passes = 1
     total_ms, total_fl, parts = 0.0, 0.0, {}
     for name, cfg, B, L in (("vit-b/16", VIT, batch_items * n_img, 197), ("roberta-base", ROBERTA, batch_items * tags, 196)):
         enc = str2encoder["transformer"](_args(**cfg))
@@ -56,13 +59,14 @@ def measure_forward(batch_items=32, tags=2, n_img=16, iters=3, passes=3, dev=Non
         enc = enc.to(dev).eval()
         emb = torch.randn(B, L, 768, device=dev)
         seg = torch.ones(B, L, dtype=torch.int64, device=dev)
+        fwd = {"split_bf16": enc, "bf16": enc.forward_bf16, "mxfp8": enc.forward_fp8}[precision]
         with torch.no_grad():
-            enc(emb, seg)
+            fwd(emb, seg)
             torch.cuda.synchronize()
             s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             s.record()
             for _ in range(iters):
-                enc(emb, seg)
+                fwd(emb, seg)
             e.record()
             torch.cuda.synchronize()
         ms = s.elapsed_time(e) / iters
@@ -73,7 +77,7 @@ def measure_forward(batch_items=32, tags=2, n_img=16, iters=3, passes=3, dev=Non
         del enc, emb
         torch.cuda.empty_cache()
     return {"ms": round(total_ms, 3), "algorithmic_tflop": round(total_fl / 1e12, 2), "tflops": round(total_fl / total_ms / 1e9, 1),
-            "mfma_issue_frac": round(passes * total_fl / total_ms / 1e9 / 2500.0, 4), "passes": passes, "parts": parts}
+            "mfma_issue_frac": round(passes * total_fl / total_ms / 1e9 / 2500.0, 4), "passes": passes, "precision": precision, "parts": parts}
 
 
 def main():
@@ -85,19 +89,23 @@ def main():
     ap.add_argument("--detail", action="store_true", help="per-signature launch averages")
     ap.add_argument("--train", action="store_true", help="time forward + backward (train mode, dropout 0.1) instead; with "
                     "--ppo-shapes: both towers at the PPO sizes (ViT over batch*16 frames, RoBERTa over batch*2 sequences)")
-    ap.add_argument("--precision", choices=("split_bf16", "mxfp8_train"), default="split_bf16",
-                    help="--train: the encoders' training precision (TransformerEncoder.fp8_train)")
+    ap.add_argument("--precision", choices=("split_bf16", "mxfp8_train", "bf16", "mxfp8"), default="split_bf16",
+                    help="--train: the encoders' training precision (TransformerEncoder.fp8_train: split_bf16 | mxfp8_train); "
+                         "--ppo-shapes without --train: the inference precision (split_bf16 | bf16 | mxfp8)")
     ap.add_argument("--recompute", action="store_true",
                     help="--train: keep each layer's input only and re-run a layer's forward in front of its backward "
                          "(TransformerEncoder.recompute); the peak-memory figure shows what that buys, the step time what it costs")
     a = ap.parse_args()
     if a.recompute and not a.train:
         ap.error("--recompute is a switch of the training schedule: give --train")
+    if a.precision in ("bf16", "mxfp8") and (a.train or not a.ppo_shapes):
+        ap.error("--precision bf16 / mxfp8 are inference modes: give --ppo-shapes, not --train")
     dev = torch.device("cuda:0")
     ops.set_gemm_passes(a.passes)
     torch.manual_seed(0)
     if a.ppo_shapes and not a.train:
-        print(measure_forward(a.batch, iters=a.iters, passes=a.passes, dev=dev))
+        prec = "split_bf16" if a.precision == "mxfp8_train" else a.precision      # (a training precision: ignored without --train)
+        print(measure_forward(a.batch, iters=a.iters, passes=a.passes, dev=dev, precision=prec))
         return
     total_ms, total_fl = 0.0, 0.0
     for name, cfg, L in (("vit-b/16", VIT, 197), ("roberta-base", ROBERTA, 196)):

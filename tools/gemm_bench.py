@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of lr2_gemm on the shapes of the LR2PPO head (run on the GPU box).
-usage: python tools/gemm_bench.py [--passes 3] [--iters 20]"""
+usage: python tools/gemm_bench.py [--passes 3] [--iters 20]
+       python tools/gemm_bench.py --bf16 [--bm 256|128] [--only ...]: the single-pass bf16 product (lr2_gemm_bf16) on the NT shapes"""
 import argparse
 import os
 import sys
@@ -26,6 +27,8 @@ SHAPES = [  # (form, M, N, K) as ops.gemm sees them
     # 31..: ViT-B/16 forward over 512 frames (M = 512 * 197) and the pointwise head at 20 tags (M = 640 * 196)
     ("NT", 100864, 768, 768), ("NT", 100864, 768, 3072), ("NT", 125440, 3072, 768), ("NT", 125440, 768, 3072),
     ("NT", 8192, 8192, 8192),
+    # 36: the QKV product of RoBERTa-base over 64 sequences (the M = 12 544 twin of shape 19)
+    ("NT", 12544, 2304, 768),
 ]
 
 
@@ -37,6 +40,8 @@ def main():
     ap.add_argument("--planes", action="store_true", help="operands as pre-split bf16 hi/lo planes (LDS-DMA path)")
     ap.add_argument("--bm", type=int, default=None, help="override block_m")
     ap.add_argument("--splits", type=int, default=None, help="override split-K factor")
+    ap.add_argument("--bf16", action="store_true", help="ONE bf16 plane per operand, one pass (ops.gemm_bf16; NT shapes only); "
+                    "--bm 256: the 256 x 256 single-pass kernel, --bm 128: the 128-row family at passes = 1; default: by size")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(0)
@@ -44,6 +49,26 @@ def main():
         if a.only is not None and si not in a.only:
             continue
         ta, tb = form == "TN", form in ("NN", "TN")
+        if a.bf16:
+            if form != "NT" or K % 64:
+                continue
+            A = torch.randn(M, K, device=dev, generator=g).to(torch.bfloat16)
+            B = torch.randn(N, K, device=dev, generator=g).to(torch.bfloat16)
+            out = torch.empty(M, N, device=dev)
+            bm = a.bm or (256 if ops.use_gemm256_b1(M, N, K) else ops._bf16_fallback_block_m(M, N))
+            for _ in range(3):
+                ops.gemm_bf16(A, B, out, M, N, K, block_m=bm)
+            torch.cuda.synchronize()
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for _ in range(a.iters):
+                ops.gemm_bf16(A, B, out, M, N, K, block_m=bm)
+            e.record()
+            torch.cuda.synchronize()
+            ms = s.elapsed_time(e) / a.iters
+            print(f"bf16x1 NT M={M:6d} N={N:6d} K={K:6d} bm={bm}: {ms:8.4f} ms  {2.0 * M * N * K / ms / 1e9:7.1f} TFLOP/s", flush=True)
+            del A, B, out
+            continue
         A = torch.randn((K, M) if ta else (M, K), device=dev, generator=g)
         B = torch.randn((K, N) if tb else (N, K), device=dev, generator=g)
         out = torch.empty(M, N, device=dev)
