@@ -197,6 +197,7 @@ int lr2_xattn_bwd(const void* Q, const void* K, const void* V, const void* dO, v
  * ELEMENTS behind each (one fused QKV matrix [batch*L, 3*heads*64] with ld = 3*heads*64 is the intended producer);
  * seg int64 [batch*L]; o fp32 [batch*L, ld_o] and/or o_hi planes (lo plane o_lo_off elements behind); hd == 64; any L (one
  * LDS-resident key block up to 256 keys, a key-block loop with running max / sum beyond).
+ * A sequence with no valid key: softmax over the -10000-shifted scores, as upstream; accurate to the fp32 grid at 10^4.
  * replaces: tencentpretrain/layers/multi_headed_attn.py:61-74 and the mask of encoders/transformer_encoder.py:62-68. */
 int lr2_self_attn_fwd(const void* q_hi, const void* k_hi, const void* v_hi, uint64_t lo_off, int ld, const int64_t* seg,
                       void* o, void* o_hi, uint64_t o_lo_off, int ld_o, void* lse, float drop_p, uint64_t drop_seed,
@@ -229,6 +230,7 @@ int lr2_first_token_attn(const void* q, int ld_q, const void* k_hi, const void* 
  *     as persistent 16-wave workgroups whose K / V (Q / dO) planes are refilled by LDS-DMA under the compute (lr2_self_attn_plan
  *     says which form a shape takes).  Shapes the persistent form does not cover fall back to the recomputing kernels, which
  *     OVERWRITE lse_ws with their own (equal up to rounding) values.
+ * A sequence with no valid key: softmax over the -10000-shifted scores, as upstream; accurate to the fp32 grid at 10^4.
  * replaces: autograd of tencentpretrain/layers/multi_headed_attn.py:61-74. */
 int lr2_self_attn_bwd(const void* q_hi, const void* k_hi, const void* v_hi, uint64_t lo_off, int ld, const void* do_hi,
                       uint64_t do_lo_off, int ld_do, const int64_t* seg, void* dq_hi, void* dk_hi, void* dv_hi,

@@ -1944,6 +1944,8 @@ int launch_fwd_blocked(const AttnArgs& a, float* o, bf16_t* oh, size_t o_lo_off,
   return lr2_launch_status("lr2_self_attn_fwd(blocked)");
 }
 
+// (tests/attn_cases.py::fwd_block restates this choice of the block length for the mask patterns of tests/test_attention_edges_gpu.py
+// and DESIGN.md 4.5 tabulates it: keep the three in step.)
 static int fwd_blocked_dispatch(const AttnArgs& a, float* o, bf16_t* oh, size_t o_lo_off, int ld_o, float* lse) {
   const int nb = (a.L + 223) / 224;
   const int tiles = (((a.L + nb - 1) / nb) + 15) / 16;       // key tiles per block
