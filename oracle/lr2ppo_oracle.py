@@ -145,14 +145,14 @@ def dropout_keep_mask(seed: int, site: int, numel: int, p: float) -> np.ndarray:
 
 def attention_keep_mask(seed: int, site: int, batch: int, heads: int, L: int, p: float) -> np.ndarray:
     """keep[b, h, q, key] of the encoders' probability dropout (lr2_self_attn_fwd / bwd): the mask stream is laid out with the key
-    dimension pitched to a multiple of 4 (csrc/selfattn.hip::mask_pitch)."""
+    dimension pitched to a multiple of 4 (csrc/selfattn_common.h::mask_pitch)."""
     pitch = (L + 3) // 4 * 4
     return np.ascontiguousarray(dropout_keep_mask(seed, site, batch * heads * L * pitch, p).reshape(batch, heads, L, pitch)[..., :L])
 
 
 def _apply_dropout(x, drop: Optional[dict], site: int, pitch4: bool = False):
     """pitch4: the mask stream pitches the LAST dimension to a multiple of 4 (the encoders' attention probabilities [b, heads, L, L]:
-    element (b, h, q, key) is index ((b * heads + h) * L + q) * pitch + key, csrc/selfattn.hip::mask_pitch)."""
+    element (b, h, q, key) is index ((b * heads + h) * L + q) * pitch + key, csrc/selfattn_common.h::mask_pitch)."""
     if drop is None or drop.get("p", 0.0) <= 0.0:
         return x
     p = float(drop["p"])

@@ -20,7 +20,7 @@ MASKS = ("suffix", "prefix_block", "hole", "alternate")
 _ROW_POW2 = torch.tensor([0.5, 1.0, 2.0])
 
 
-# ---- the dispatch, restated from lr2ppo_amd/csrc/selfattn.hip (lr2_self_attn_fwd / fwd_blocked_dispatch / lr2_self_attn_bwd) and
+# ---- the dispatch, restated from lr2ppo_amd/csrc/selfattn_fwd.hip (lr2_self_attn_fwd / fwd_blocked_dispatch), selfattn_bwd.hip (lr2_self_attn_bwd) and
 # selfattn_mx.hip (lr2_self_attn_fwd_bf16); DESIGN.md 4.5 has the table.  `persistent` = batch * heads >= the CU count. ----
 def fwd_block(L):
     """Key-block length of the forward at this L."""

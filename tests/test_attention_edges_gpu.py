@@ -1,4 +1,4 @@
-"""Self-attention kernels (csrc/selfattn.hip, csrc/selfattn_mx.hip) on inputs whose scores are exact, at the edges of the softmax, of the
+"""Self-attention kernels (csrc/selfattn_fwd.hip, csrc/selfattn_bwd.hip, csrc/selfattn_mx.hip) on inputs whose scores are exact, at the edges of the softmax, of the
 key mask and of the length dispatch.  Case builders and the fp64 reference: tests/attn_cases.py (checked by test_attention_edges_cpu.py).
 
 Which form a call runs ("Self-attention: which length runs which kernel"; `persistent` = batch * heads >= the CU count):

@@ -366,6 +366,23 @@ def test_no_kernel_in_the_library_spills_registers(native):
     assert all(k["vgpr"] <= 512 for k in ks)                   # .vgpr_count = architectural + accumulation registers
 
 
+def test_build_lists_name_every_source_and_every_included_header():
+    """_native.build() compiles SOURCES and _native._stale() watches SOURCES + HEADERS: a .hip file missing from the first is
+    never compiled, a header missing from the second can be edited without the library being rebuilt."""
+    from lr2ppo_amd import _native
+    assert sorted(f for f in os.listdir(_native.CSRC) if f.endswith(".hip")) == sorted(_native.SOURCES)
+    listed = {os.path.realpath(h) for h in _native.HEADERS}
+    assert all(os.path.isfile(h) for h in listed)
+    files = [os.path.join(_native.CSRC, s) for s in _native.SOURCES] + sorted(listed)
+    included = set()
+    for f in files:
+        for name in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(f).read(), re.M):
+            hits = [p for d in (os.path.dirname(f), _native.CSRC, _native.INCLUDE) if os.path.isfile(p := os.path.join(d, name))]
+            assert hits, (f, name)
+            included.add(os.path.realpath(hits[0]))
+    assert included and included <= listed, sorted(included - listed)
+
+
 def test_wgrad_tiling_picks_the_tn256_kernel_for_long_contractions():
     """Host logic (no launch): weight gradients of the encoders / heads at >= 4096 token rows go to the TN 256 kernel with
     tiles x splits in one round of the chip; short contractions and the 2 GB out_layer.fc1 matrix do not."""

@@ -98,7 +98,7 @@ def test_row_split_is_what_runs(dev):
     assert [c3[i] - c2[i] for i in range(3)] == [1, 0, 0]
 
 
-# ---- persistent attention kernels (csrc/selfattn.hip: self_attn_persist_kernel, self_attn_bwd_{dq,dkv}_persist_kernel) ----
+# ---- persistent attention kernels (csrc/selfattn_fwd.hip: self_attn_persist_kernel; csrc/selfattn_bwd.hip: self_attn_bwd_{dq,dkv}_persist_kernel) ----
 def _attn_case(dev, batch, heads, L, seed):
     from lr2ppo_amd import ops
     E = heads * 64
