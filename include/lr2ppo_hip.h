@@ -24,7 +24,7 @@ extern "C" {
 #define LR2_ERR_SHAPE (-2)  /* shape not supported by the kernel's tiling */
 #define LR2_ERR_LAUNCH (-3) /* HIP launch failure */
 
-#define LR2_ABI_VERSION 21
+#define LR2_ABI_VERSION 22
 int lr2_abi_version(void);
 /* Fills name[0..len) with the HIP device name and returns the CU count (or <0). */
 int lr2_device_info(char* name, int len);
@@ -173,8 +173,8 @@ int lr2_layernorm_bwd(const void* dy, int group, uint64_t group_stride, const vo
 /* out[c] = sum_b partials[b*ld + c] for c < cols (deterministic second stage of column reductions). */
 int lr2_colsum_partials_finish(const void* partials, int nblocks, int cols, int ld, void* out, int accumulate,
                                void* stream);
-/* Column sums of a [rows, cols] matrix (fp32, or bf16 planes with the lo plane lo_off elements after the hi plane)
- * -> fp32 [cols] (bias gradients); partials: workspace [nblocks][cols].
+/* Column sums of a [rows, cols] matrix (fp32, or bf16 planes with the lo plane lo_off elements after the hi plane; is_planes == 2
+ * (ABI 22): ONE bf16 plane, lo_off unused) -> fp32 [cols] (bias gradients); partials: workspace [nblocks][cols].
  * replaces: autograd of the nn.Linear bias add. */
 int lr2_colsum(const void* x, int is_planes, uint64_t lo_off, int rows, int cols, int ld, void* partials, int nblocks,
                void* out, void* stream);
@@ -419,6 +419,34 @@ int lr2_gemm_bf16(const void* A, const void* B, int M, int N, int K, int lda, in
  * the general kernel family (no device call).  Plain host counters, as lr2_gemm_launch_counts': not synchronised -- meaningful when one
  * thread issues the launches, which is how tests read them. */
 int lr2_gemm_bf16_launch_counts(uint64_t counts[2]);
+
+/* ABI 22.  Single-pass bf16 products of encoder TRAINING (FeatureExtractor(precision="bf16_train")): A and B ONE bf16 plane
+ * each, one v_mfma_f32_16x16x32_bf16 product per tile pair, fp32 accumulate.  NOT the parity path (lr2_gemm at passes = 3 stays it).
+ *   (trans_a, trans_b) == (0, 0):  C[M, N] = A[M, K] . B[N, K]^T -- lr2_gemm_bf16's product with lr2_gemm's TRAINING epilogue: alpha, bias,
+ *       act 0 / 1 (GELU; out_z keeps the pre-activation) / 2 (multiply by the EXACT GELU'(aux_z): x * (Phi(z) + z phi(z)) formed in fp64
+ *       with one rounding, on kernels of its own; no split-K), the dropout mask (drop_*), resid, accumulate; the
+ *       result goes to out (fp32) and / or out_hi (hi / lo planes, or ONE plane when out_lo_off == 0).  K % 64 == 0.  block_m == 256: the
+ *       256 x 256 single-pass kernel (csrc/gemm256_b1.hip) when at most one of {aux_z, resid, accumulate} asks for a value per element
+ *       and splits <= 1, following lr2_gemm_row_split_plan unless a dropout mask is fused (lr2_gemm's rule); else the general family at
+ *       passes = 1 (block_m 128 / 64).  An input gradient runs in this form on the weight's transpose (lr2_split_planes_t).
+ *   (1, 1):  C[M, N] = A[K, M]^T . B[K, N] -- the weight gradient dW[N_out, N_in] = dY[T, N_out]^T X[T, N_in] (M = N_out, N = N_in, K = T;
+ *       any K: rows past a_bytes / b_bytes -- the EXACT plane extents -- read as zero).  Plain epilogue (alpha -> out).  colsum (with
+ *       colsum_ws of max(128, splits * ceil(N / 256)) * M floats; M % 4 == 0): the bias gradient db[m] = sum_k A[k, m], the column sums
+ *       of the bf16 plane AS THE PRODUCT SEES IT (not of the fp32 gradient it was rounded from).  block_m == 256: the 256 x 256
+ *       single-pass TN kernel (csrc/gemm256_tn_b1.hip; 64-row K steps, tiles x splits workgroups, column sums from the same launch);
+ *       else the general family at passes = 1 and lr2_colsum.  splits > 1 leaves fp32 slabs [splits, M, N] in splitk_ws, summed in
+ *       split order by one more launch: the same bits on every run.
+ * LR2_ERR_ARG: NULL operands / epilogue / no output; act == 2 without aux_z; adam_p (no fused optimizer); accumulate or a training
+ * epilogue (bias, act, dropout, resid, out_z, out_hi) with the (1,1) form; colsum with the (0,0) form or without colsum_ws; (1,0) / (0,1);
+ * splits > 1 without splitk_ws or with act == 2.  LR2_ERR_SHAPE: lda / ldb % 8, N % 4, an epilogue leading dimension % 4, K % 64 in the (0,0) form,
+ * M % 4 with colsum, a_bytes / b_bytes >= 4 GiB.  Nothing is launched by a rejected call.
+ * replaces: nn.Linear forward and autograd's input / weight / bias gradients of it (tencentpretrain/layers/position_ffn.py:12-15,
+ * multi_headed_attn.py:55-76) in that mode. */
+int lr2_gemm_bf16_train(const void* A, const void* B, int M, int N, int K, int lda, int ldb, int trans_a, int trans_b, uint64_t a_bytes,
+                        uint64_t b_bytes, const lr2_epilogue* epi, void* splitk_ws, int splits, int block_m, void* stream);
+/* Diagnostic, as lr2_gemm_bf16_launch_counts: launches issued by lr2_gemm_bf16_train -- counts[0] the 256 x 256 single-pass NT kernel,
+ * counts[1] the 256 x 256 single-pass TN kernel, counts[2] the general kernel family. */
+int lr2_gemm_bf16_train_launch_counts(uint64_t counts[3]);
 
 /* ABI 20.  MX-FP8 encoder training (FeatureExtractor(precision="mxfp8_train")): the backward's operands, blocked along the axis its
  * products reduce over, and a K-sliced weight-gradient product.

@@ -324,7 +324,8 @@ __device__ __forceinline__ void compute_tile(const char* a_hi, const char* b_hi,
 }
 
 // ---- the kernel ------------------------------------------------------------------------------------
-template <int BM, int BN, int BK, int WM, int WN, bool TA, bool TB, int PASSES, bool APL, bool BPL, int NW = 4>
+// (EXACT: the two instantiations lr2_gemm_bf16_train launches for act == 2 -- the epilogue multiplies by gemm_common.h::mul_gelu_grad_exact)
+template <int BM, int BN, int BK, int WM, int WN, bool TA, bool TB, int PASSES, bool APL, bool BPL, int NW = 4, bool EXACT = false>
 // 8-wave workgroups are meant to run two per CU = 4 waves per SIMD: cap the register allocation at 128 for them
 __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 1) void gemm_kernel(GemmParams g) {
   static_assert(NW == 4 || (APL && BPL), "8-wave workgroups exist for planes x planes operands only");
@@ -436,7 +437,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 1) void gemm_kernel(GemmPara
   float* slab = reinterpret_cast<float*>(smem) + wave * (32 * (WN + 4));
   float* part = g.partial ? g.partial + (size_t)split * (size_t)g.M * (size_t)g.N : nullptr;
   if (g.epi.adam_p && !part) epilogue_wave_adam<WM, WN, MI, NI, ((APL && BPL) ? (NW == 8 ? 1 : 0) : -1)>(g, acc, slab, m0 + wm0, n0 + wn0, lane);
-  else epilogue_wave<WM, WN, MI, NI, 3, ((APL && BPL) ? (NW == 8 ? 1 : 0) : -1)>(g, acc, slab, m0 + wm0, n0 + wn0, lane, part);
+  else epilogue_wave<WM, WN, MI, NI, 3, ((APL && BPL) ? (NW == 8 ? 1 : 0) : -1), EXACT>(g, acc, slab, m0 + wm0, n0 + wn0, lane, part);
 }
 
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ partial, int splits, int M, int N,
@@ -475,6 +476,8 @@ constexpr int gemm_bk(bool apl, bool bpl, bool tb) { return (apl && bpl && tb) ?
   LR2_GEMM_INST_FORM(false, false, APL, BPL)  \
   LR2_GEMM_INST_FORM(false, true, APL, BPL)   \
   LR2_GEMM_INST_FORM(true, true, APL, BPL)
+template __global__ void gemm_kernel<64, 128, 64, 64, 32, false, false, 1, true, true, 4, true>(GemmParams);     // lr2_gemm_bf16_train, act == 2
+template __global__ void gemm_kernel<128, 128, 64, 64, 64, false, false, 1, true, true, 4, true>(GemmParams);
 LR2_GEMM_INST_FORMS(false, false)
 LR2_GEMM_INST_FORMS(true, false)
 LR2_GEMM_INST_FORM(true, true, true, true)
@@ -528,6 +531,27 @@ int dispatch_form(const GemmParams& p, int splits, int bm, int passes, int ta, i
   return LR2_ERR_ARG;  // (1,0) is not a form the path needs
 }
 
+// lr2_gemm_bf16_train, act == 2, no split-K: launch<BM, false, false, 1, true, true> on the EXACT instantiation
+template <int BM>
+int launch_exact(const GemmParams& p_in, hipStream_t stream) {
+  constexpr int BN = 128, BK = 64, NW = 4, WN = BM == 128 ? 64 : 32;
+  GemmParams p = p_in;
+  p.tiles_m = (p.M + BM - 1) / BM;
+  p.tiles_n = (p.N + BN - 1) / BN;
+  p.splits = 1;
+  p.dma_stages = 1;
+  constexpr size_t main_lds = (size_t)(BM + BN) * BK * 2, epi_lds = (size_t)NW * 32 * (WN + 4) * 4;
+  constexpr size_t lds = main_lds > epi_lds ? main_lds : epi_lds;
+  auto kern = gemm_kernel<BM, BN, BK, 64, WN, false, false, 1, true, true, NW, true>;
+  static bool attr_set = false;
+  if (!attr_set) {
+    if (lr2_allow_dynamic_lds(kern, lds, "gemm(exact GELU')")) return LR2_ERR_LAUNCH;
+    attr_set = true;
+  }
+  LR2_LAUNCH(kern, dim3(p.tiles_m * p.tiles_n), dim3(64 * NW), lds, stream, p);
+  return lr2_launch_status(__func__);
+}
+
 Epilogue to_device_epilogue(const lr2_epilogue* e) {
   Epilogue d{};
   d.bias = (const float*)e->bias;
@@ -578,6 +602,8 @@ Epilogue to_device_epilogue(const lr2_epilogue* e) {
 int launch_gemm256_nt(const GemmParams& p, hipStream_t stream);   // gemm256.hip
 int launch_gemm256_tn(const GemmParams& p, int splits, hipStream_t stream);
 int launch_gemm256_b1(const GemmParams& p, hipStream_t stream);   // gemm256_b1.hip
+int launch_gemm256_b1_exact(const GemmParams& p, hipStream_t stream);
+int launch_gemm256_tn_b1(const GemmParams& p, int splits, hipStream_t stream);   // gemm256_tn_b1.hip
 
 }  // namespace lr2gemm
 using namespace lr2gemm;
@@ -792,4 +818,109 @@ extern "C" int lr2_gemm_bf16(const void* A, const void* B, int M, int N, int K, 
   }
   ++g_launches_b1[0];
   return launch_gemm256_b1(p, s);
+}
+
+// ---- single-pass bf16 products of encoder training (the "bf16_train" mode): forward / input gradient (NT) and weight gradient (TN) ----
+static uint64_t g_launches_b1t[3] = {0, 0, 0};     // 256 x 256 NT, 256 x 256 TN, the general family at passes = 1
+extern "C" int lr2_gemm_bf16_train_launch_counts(uint64_t counts[3]) {
+  if (!counts) return LR2_ERR_ARG;
+  for (int i = 0; i < 3; ++i) counts[i] = g_launches_b1t[i];
+  return 0;
+}
+
+extern "C" int lr2_gemm_bf16_train(const void* A, const void* B, int M, int N, int K, int lda, int ldb, int trans_a, int trans_b,
+                                   uint64_t a_bytes, uint64_t b_bytes, const lr2_epilogue* epi, void* splitk_ws, int splits, int block_m,
+                                   void* stream) {
+  if (!A || !B || M <= 0 || N <= 0 || K <= 0 || !epi || (!epi->out && !epi->out_hi)) return LR2_ERR_ARG;
+  if ((trans_a != 0) != (trans_b != 0)) return LR2_ERR_ARG;                    // NT and TN only
+  const bool tn = trans_a != 0;
+  if (epi->adam_p) return LR2_ERR_ARG;                                         // no fused optimizer step in this mode
+  if (epi->act < 0 || epi->act > 2 || (epi->act == 2 && !epi->aux_z)) return LR2_ERR_ARG;
+  if (epi->out_z && epi->act != 1) return LR2_ERR_ARG;
+  if (epi->accumulate && (tn || !epi->out)) return LR2_ERR_ARG;
+  if (epi->drop_seed_dev && epi->drop_site >= 65536u) return LR2_ERR_ARG;
+  if (tn && (epi->bias || epi->act || epi->drop_p > 0.f || epi->resid || epi->out_hi || !epi->out)) return LR2_ERR_ARG;   // plain epilogue
+  if (epi->colsum && (!tn || !epi->colsum_ws)) return LR2_ERR_ARG;             // weight-gradient form only
+  if (splits > 1 && !splitk_ws) return LR2_ERR_ARG;
+  if (epi->act == 2 && splits > 1) return LR2_ERR_ARG;                         // the split-K reducer has no exact-GELU' form
+  if (!tn && (K % 64)) return LR2_ERR_SHAPE;                                   // K-contiguous operands: whole 64-deep K steps
+  if ((lda % 8) || (ldb % 8) || (N % 4) || (epi->colsum && (M % 4))) return LR2_ERR_SHAPE;
+  if ((epi->out && epi->ld_out % 4) || (epi->out_z && epi->ld_z % 4) || (epi->resid && epi->ld_resid % 4) ||
+      (epi->aux_z && epi->ld_aux % 4) || (epi->out_hi && epi->ld_planes % 4))
+    return LR2_ERR_SHAPE;
+  if (a_bytes >= (1ull << 32) || b_bytes >= (1ull << 32)) return LR2_ERR_SHAPE;
+  const bool fits256 = block_m == 256 && a_bytes <= 0xFFFFFD00ull && b_bytes <= 0xFFFFFD00ull;
+  const bool use256nt = fits256 && !tn && splits <= 1 &&
+                        ((epi->act == 2) + (epi->resid != nullptr) + (epi->accumulate != 0)) <= 1;   // one request slot per element
+  const bool use256tn = fits256 && tn;
+  if (block_m != 64) block_m = 128;
+  const int BK = use256tn ? 64 : (tn ? gemm_bk(true, true, true) : 64);
+  if (splits < 1) splits = 1;
+  const int total_k_tiles = (K + BK - 1) / BK;
+  if (splits > total_k_tiles) splits = total_k_tiles;
+  GemmParams p{};
+  p.A = A;
+  p.B = B;
+  p.M = M;
+  p.N = N;
+  p.K = K;
+  p.lda = lda;
+  p.ldb = ldb;
+  p.a_bytes = (uint32_t)a_bytes;
+  p.b_bytes = (uint32_t)b_bytes;
+  p.k_tiles_per_split = (total_k_tiles + splits - 1) / splits;
+  splits = (total_k_tiles + p.k_tiles_per_split - 1) / p.k_tiles_per_split;
+  p.partial = splits > 1 ? (float*)splitk_ws : nullptr;
+  p.epi = to_device_epilogue(epi);
+  p.epi.store_nt = (uint64_t)M * (uint64_t)N * (epi->out ? 4ull : 2ull) >= (256ull << 20) ? 1 : 0;   // lr2_gemm_bf16's rule
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  // act == 2 (the FFN-2 input gradient): the kernels whose epilogue multiplies by the exact GELU' with one rounding
+  const bool exact = epi->act == 2;
+  if (use256nt) {
+    // the row split of lr2_gemm, and its exception: a fused dropout mask indexes elements from the launch's first row
+    int M1 = 0, bm2 = 128;
+    if (epi->drop_p <= 0.f && lr2_gemm_row_split_plan(M, N, K, &M1, &bm2) == 0 && M1 > 0) {
+      GemmParams p1 = p;
+      p1.M = M1;
+      rc = exact ? launch_gemm256_b1_exact(p1, s) : launch_gemm256_b1(p1, s);
+      if (rc) return rc;
+      ++g_launches_b1t[0];
+      ++g_launches_b1t[2];
+      GemmParams p2 = p;
+      p2.M = M - M1;
+      p2.A = (const char*)A + (size_t)M1 * (size_t)lda * 2u;
+      p2.a_bytes = (uint32_t)(a_bytes - (uint64_t)M1 * (uint64_t)lda * 2u);
+      Epilogue& e2 = p2.epi;
+      if (e2.resid) e2.resid += (size_t)M1 * e2.ld_resid;
+      if (e2.aux_z) e2.aux_z += (size_t)M1 * e2.ld_aux;
+      if (e2.out) e2.out += (size_t)M1 * e2.ld_out;
+      if (e2.out_z) e2.out_z += (size_t)M1 * e2.ld_z;
+      if (e2.out_hi) e2.out_hi += (size_t)M1 * e2.ld_planes;
+      if (exact) return bm2 == 64 ? launch_exact<64>(p2, s) : launch_exact<128>(p2, s);
+      return dispatch_form<true, true>(p2, 1, bm2, 1, 0, 0, s);
+    }
+    ++g_launches_b1t[0];
+    return exact ? launch_gemm256_b1_exact(p, s) : launch_gemm256_b1(p, s);
+  }
+  const bool fused_colsum = use256tn && epi->colsum;
+  if (fused_colsum) p.epi.colsum_partial = (float*)epi->colsum_ws;
+  ++g_launches_b1t[use256tn ? 1 : 2];
+  if (use256tn) rc = launch_gemm256_tn_b1(p, splits, s);
+  else if (exact) rc = block_m == 64 ? launch_exact<64>(p, s) : launch_exact<128>(p, s);
+  else rc = dispatch_form<true, true>(p, splits, block_m, 1, tn ? 1 : 0, tn ? 1 : 0, s);
+  if (rc) return rc;
+  if (splits > 1) {
+    const size_t total4 = (size_t)M * N / 4;
+    int blocks = (int)((total4 + 255) / 256);
+    if (blocks > 2048) blocks = 2048;
+    LR2_LAUNCH(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, s, (const float*)splitk_ws, splits, M, N, p.epi);
+    if (lr2_launch_status(__func__)) return LR2_ERR_LAUNCH;
+  }
+  if (epi->colsum) {
+    if (fused_colsum)
+      return lr2_colsum_partials_finish(epi->colsum_ws, splits * ((N + 255) / 256), M, M, epi->colsum, 0, stream);
+    return lr2_colsum(A, 2, 0, K, M, lda, epi->colsum_ws, K < 128 ? K : 128, epi->colsum, stream);
+  }
+  return 0;
 }

@@ -44,7 +44,9 @@ struct HalfProducts {
 };
 
 // MIH = accumulator tiles per half of a wave's rows: 4 -> the 256 x 256 tile; 3 -> the 192 x 256 tile of gemm256.hip.
-template <int MIH>
+// EXACT: the instantiations lr2_gemm_bf16_train launches for act == 2 (the FFN-2 input gradient of the "bf16_train" mode): that epilogue
+// multiplies by gemm_common.h::mul_gelu_grad_exact; everything else is the same.
+template <int MIH, bool EXACT = false>
 __global__ __launch_bounds__(512, 2) void gemm256_b1_kernel(GemmParams g) {
   constexpr int BMT = 64 * MIH, WMT = 32 * MIH;      // tile rows, wave-tile rows
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -77,7 +79,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_b1_kernel(GemmParams g) {
   drain(wr);
 
   float* slab = reinterpret_cast<float*>(smem) + wave * (32 * (64 + 4));
-  epilogue_wave<WMT, 64, 2 * MIH, 4, 1, 3>(g, acc, slab, m0 + wr * WMT, n0 + wc * 64, lane, nullptr);
+  epilogue_wave<WMT, 64, 2 * MIH, 4, 1, 3, EXACT>(g, acc, slab, m0 + wr * WMT, n0 + wc * 64, lane, nullptr);
 }
 
 }  // namespace g256b
@@ -100,6 +102,24 @@ int launch_gemm256_b1(const GemmParams& p_in, hipStream_t stream) {
   }
   if (bm == 192) LR2_LAUNCH(gemm256_b1_kernel<3>, dim3(p.tiles_m * p.tiles_n), dim3(512), LDS_BYTES, stream, p);
   else LR2_LAUNCH(gemm256_b1_kernel<4>, dim3(p.tiles_m * p.tiles_n), dim3(512), LDS_BYTES, stream, p);
+  return lr2_launch_status(__func__);
+}
+
+// Host entry for lr2_gemm_bf16_train's act == 2 products (the FFN-2 input gradient): the same launch on the EXACT instantiations.
+int launch_gemm256_b1_exact(const GemmParams& p_in, hipStream_t stream) {
+  using namespace g256b;
+  GemmParams p = p_in;
+  const int bm = gemm256_nt_tile_rows(p.M, p.N);
+  p.tiles_m = (p.M + bm - 1) / bm;
+  p.tiles_n = (p.N + BN - 1) / BN;
+  static bool attr_set = false;
+  if (!attr_set) {
+    if (lr2_allow_dynamic_lds((gemm256_b1_kernel<4, true>), LDS_BYTES, "gemm256_b1(exact GELU')")) return LR2_ERR_LAUNCH;
+    if (lr2_allow_dynamic_lds((gemm256_b1_kernel<3, true>), LDS_BYTES, "gemm256_b1(192 rows, exact GELU')")) return LR2_ERR_LAUNCH;
+    attr_set = true;
+  }
+  if (bm == 192) LR2_LAUNCH((gemm256_b1_kernel<3, true>), dim3(p.tiles_m * p.tiles_n), dim3(512), LDS_BYTES, stream, p);
+  else LR2_LAUNCH((gemm256_b1_kernel<4, true>), dim3(p.tiles_m * p.tiles_n), dim3(512), LDS_BYTES, stream, p);
   return lr2_launch_status(__func__);
 }
 

@@ -125,7 +125,16 @@ __device__ __forceinline__ float4 scale_bias4(const Epilogue& e, float4 v, float
                        __builtin_fmaf(e.alpha, v.w, b.w));
   return make_float4(e.alpha * v.x, e.alpha * v.y, e.alpha * v.z, e.alpha * v.w);
 }
-template <int NS>
+// x * GELU'(z) with ONE rounding: GELU'(z) = Phi(z) + z phi(z) and the product in fp64 (the "bf16_train" mode's FFN-2 input gradient,
+// lr2_gemm_bf16_train: within half an ulp of the exact value).  gelu_erf_grad (common.h) -- erf_fast, up to 2.7 x 2^-23 from the exact
+// GELU' -- stays what every other path multiplies by.
+__device__ __forceinline__ float mul_gelu_grad_exact(float x, float z) {
+  const double zd = (double)z;
+  const double g = 0.5 * erfc(-0.70710678118654752440 * zd) + zd * 0.39894228040143267794 * exp(-0.5 * zd * zd);
+  return (float)((double)x * g);
+}
+// EXACT (kernels instantiated for lr2_gemm_bf16_train only): act == 2 multiplies by mul_gelu_grad_exact
+template <int NS, bool EXACT = false>
 __device__ __forceinline__ void epilogue_apply4(const Epilogue& e, float4 v, float4 b, const EpiLoads<NS>& L, int m, int n, int N) {
 #pragma clang fp contract(off)      // one rounding per written operation, whatever path forms the element (see epilogue_fast)
   constexpr int SR = NS == 3 ? 1 : 0, SO = NS == 3 ? 2 : 0;
@@ -140,7 +149,12 @@ __device__ __forceinline__ void epilogue_apply4(const Epilogue& e, float4 v, flo
   }
   if (e.act == 2) {
     const float4 z = L.s[0];
-    v.x *= gelu_erf_grad(z.x); v.y *= gelu_erf_grad(z.y); v.z *= gelu_erf_grad(z.z); v.w *= gelu_erf_grad(z.w);
+    if constexpr (EXACT) {
+      v.x = mul_gelu_grad_exact(v.x, z.x); v.y = mul_gelu_grad_exact(v.y, z.y);
+      v.z = mul_gelu_grad_exact(v.z, z.z); v.w = mul_gelu_grad_exact(v.w, z.w);
+    } else {
+      v.x *= gelu_erf_grad(z.x); v.y *= gelu_erf_grad(z.y); v.z *= gelu_erf_grad(z.z); v.w *= gelu_erf_grad(z.w);
+    }
   }
   if (e.resid) { v.x += L.s[SR].x; v.y += L.s[SR].y; v.z += L.s[SR].z; v.w += L.s[SR].w; }
   if (NS == 3 && e.adam_p) {  // fused optimizer step
@@ -359,7 +373,7 @@ __device__ __forceinline__ bool epilogue_fast_dispatch(const Epilogue& e, const 
   return false;
 }
 
-template <int WN, int HALF, int NS, int WIDE>
+template <int WN, int HALF, int NS, int WIDE, bool EXACT = false>
 __device__ __forceinline__ void epilogue_from_slab(const GemmParams& g, float* slab, int mw, int nw, int lane, float* partial,
                                                    float4 bias4, const EpiSlab<WN, NS>& S) {
   constexpr int LDW = WN + 4;
@@ -374,14 +388,18 @@ __device__ __forceinline__ void epilogue_from_slab(const GemmParams& g, float* s
   __builtin_amdgcn_sched_barrier(0);
   // (LR2_GEMM_EPI_GENERAL=1 switches the fast forms off: tools/dbg/fuzz_epilogue.py compares the two paths bit for bit)
   if (!partial && !g.epi_general && mw + 32 * HALF + 32 <= g.M && nw + WN <= g.N) {   // wave-uniform: the slab lies inside the matrix
-    if (epilogue_fast_dispatch<NP, RPP, NS, WIDE>(g.epi, v, bias4, S.L, mw + 32 * HALF + row0, n, g.N)) return;
+    if constexpr (EXACT) {      // (the straight-line forms multiply by gelu_erf_grad)
+      if (g.epi.act != 2 && epilogue_fast_dispatch<NP, RPP, NS, WIDE>(g.epi, v, bias4, S.L, mw + 32 * HALF + row0, n, g.N)) return;
+    } else {
+      if (epilogue_fast_dispatch<NP, RPP, NS, WIDE>(g.epi, v, bias4, S.L, mw + 32 * HALF + row0, n, g.N)) return;
+    }
   }
 #pragma unroll
   for (int pass = 0; pass < NP; ++pass) {
     const int m = mw + 32 * HALF + pass * RPP + row0;
     if (m < g.M && n < g.N) {
       if (partial) st4(partial + (size_t)m * g.N + n, v[pass]);
-      else epilogue_apply4<NS>(g.epi, v[pass], bias4, S.L[pass], m, n, g.N);
+      else epilogue_apply4<NS, EXACT>(g.epi, v[pass], bias4, S.L[pass], m, n, g.N);
     }
   }
 }
@@ -389,7 +407,7 @@ __device__ __forceinline__ void epilogue_from_slab(const GemmParams& g, float* s
 // PIPE: request slab h+1's HBM operands before slab h's stores (after slab h's accumulators have moved to LDS, so the
 // register peak is acc - 32 + 3 x 32 for NS = 1).  Kernels that keep up to three requests per element (NS = 3) and run
 // several workgroups per CU request per slab instead: their register budget decides their occupancy.
-template <int WM, int WN, int MI, int NI, int NS, int HALF, bool PIPE, int WIDE>
+template <int WM, int WN, int MI, int NI, int NS, int HALF, bool PIPE, int WIDE, bool EXACT = false>
 __device__ __forceinline__ void epilogue_pipeline(const GemmParams& g, f32x4_t (&acc)[MI][NI], float* slab, int mw, int nw,
                                                   int lane, float* partial, float4 bias4, EpiSlab<WN, NS>& cur) {
   if constexpr (!PIPE) {
@@ -400,12 +418,12 @@ __device__ __forceinline__ void epilogue_pipeline(const GemmParams& g, f32x4_t (
   if constexpr (PIPE && HALF + 1 < WM / 32) {
     if (!partial) epilogue_request<WN, NS, HALF + 1>(g, next, mw, nw, lane);
   }
-  epilogue_from_slab<WN, HALF, NS, WIDE>(g, slab, mw, nw, lane, partial, bias4, cur);
+  epilogue_from_slab<WN, HALF, NS, WIDE, EXACT>(g, slab, mw, nw, lane, partial, bias4, cur);
   if constexpr (HALF + 1 < WM / 32)
-    epilogue_pipeline<WM, WN, MI, NI, NS, HALF + 1, PIPE, WIDE>(g, acc, slab, mw, nw, lane, partial, bias4, PIPE ? next : cur);
+    epilogue_pipeline<WM, WN, MI, NI, NS, HALF + 1, PIPE, WIDE, EXACT>(g, acc, slab, mw, nw, lane, partial, bias4, PIPE ? next : cur);
 }
 
-template <int WM, int WN, int MI, int NI, int NS = 3, int WIDE = (NS == 1 ? 2 : 0)>
+template <int WM, int WN, int MI, int NI, int NS = 3, int WIDE = (NS == 1 ? 2 : 0), bool EXACT = false>
 __device__ __forceinline__ void epilogue_wave(const GemmParams& g, f32x4_t (&acc)[MI][NI], float* slab, int mw, int nw,
                                               int lane, float* partial) {
   static_assert(WM == 32 || WM == 64 || WM == 96 || WM == 128, "wave tile rows");
@@ -422,7 +440,7 @@ __device__ __forceinline__ void epilogue_wave(const GemmParams& g, f32x4_t (&acc
   // them -- and with loads and stores on one in-order counter the only wait it can write there is vmcnt(0): every slab waited for
   // the stores of the slab before it, one HBM write latency each (12 us of a 67-us K = 768 tile, profiles/experiments/README.md E).
   asm volatile("" ::"v"(bias4.x), "v"(bias4.y), "v"(bias4.z), "v"(bias4.w));
-  epilogue_pipeline<WM, WN, MI, NI, NS, 0, PIPE, WIDE>(g, acc, slab, mw, nw, lane, partial, bias4, first);
+  epilogue_pipeline<WM, WN, MI, NI, NS, 0, PIPE, WIDE, EXACT>(g, acc, slab, mw, nw, lane, partial, bias4, first);
 }
 
 // Fused AdamW epilogue: the weight, exp_avg and exp_avg_sq vectors of all 32 rows of a slab are requested BEFORE the

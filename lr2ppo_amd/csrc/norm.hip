@@ -245,6 +245,27 @@ __global__ __launch_bounds__(256) void colsum_kernel(const void* __restrict__ x_
   *reinterpret_cast<float4*>(partials + (size_t)blockIdx.y * cols + c) = s;
 }
 
+// the same for ONE bf16 plane (is_planes == 2: the operand of the single-pass products, lr2_gemm_bf16_train's bias gradient)
+__global__ __launch_bounds__(256) void colsum_plane_kernel(const bf16_t* __restrict__ x, int rows, int cols, int ld,
+                                                           float* __restrict__ partials) {
+  const int c = (blockIdx.x * 256 + threadIdx.x) * 4;
+  if (c >= cols) return;
+  const int chunk = (rows + gridDim.y - 1) / gridDim.y;
+  const int r0 = blockIdx.y * chunk;
+  int r1 = r0 + chunk;
+  if (r1 > rows) r1 = rows;
+  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll 8
+  for (int r = r0; r < r1; ++r) {
+    const u32x2_t h = *reinterpret_cast<const u32x2_t*>(x + (size_t)r * ld + c);
+    s.x += __uint_as_float(h[0] << 16);
+    s.y += __uint_as_float(h[0] & 0xffff0000u);
+    s.z += __uint_as_float(h[1] << 16);
+    s.w += __uint_as_float(h[1] & 0xffff0000u);
+  }
+  *reinterpret_cast<float4*>(partials + (size_t)blockIdx.y * cols + c) = s;
+}
+
 }  // namespace
 
 extern "C" int lr2_layernorm_fwd(const void* x, const void* gamma, const void* beta, void* out, void* out_hi,
@@ -308,7 +329,9 @@ extern "C" int lr2_colsum(const void* x, int is_planes, uint64_t lo_off, int row
   if (cols % 4 != 0 || ld % 4 != 0) return LR2_ERR_SHAPE;
   if (nblocks > rows) nblocks = rows;
   dim3 grid((cols + 1023) / 1024, nblocks);
-  if (is_planes)
+  if (is_planes == 2)
+    LR2_LAUNCH(colsum_plane_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, rows, cols, ld, (float*)partials);
+  else if (is_planes)
     LR2_LAUNCH(colsum_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, x, (size_t)lo_off, rows, cols, ld, (float*)partials);
   else
     LR2_LAUNCH(colsum_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, x, (size_t)0, rows, cols, ld, (float*)partials);

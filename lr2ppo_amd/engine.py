@@ -55,6 +55,15 @@ class Workspace:
             self._bufs[key] = b
         return Planes(b, rows, cols)
 
+    def plane(self, name: str, rows: int, cols: int) -> torch.Tensor:
+        """[rows * cols] bf16 as int16: ONE plane (the operand of the single-pass bf16 products)."""
+        key = "p1:" + name
+        b = self._bufs.get(key)
+        if b is None or b.numel() < rows * cols:
+            b = torch.empty(max(rows * cols, 8), dtype=torch.int16, device=self.device)
+            self._bufs[key] = b
+        return b[:rows * cols]
+
     def bytes(self) -> int:
         return sum(b.numel() * b.element_size() for b in self._bufs.values())
 
@@ -87,6 +96,9 @@ class Arena:
 
     def planes(self, rows: int, cols: int) -> Planes:
         return Planes(self._take(4 * rows * cols).view(torch.int16), rows, cols)
+
+    def plane(self, rows: int, cols: int) -> torch.Tensor:
+        return self._take(2 * rows * cols).view(torch.int16)
 
 
 class DropCfg:
@@ -213,6 +225,26 @@ def linear_wgrad(ws, dy, x, dw, db, M, N_in, N_out):
     if db is not None and not fused:
         nb = min(512 if N_out <= 1024 else 256, M)     # row chunks: enough workgroups to fill 256 CUs at 1024 columns each
         ops.colsum(dy, db, ws.vec("colsum_partials", nb * N_out), rows=M, cols=N_out, nblocks=nb)
+
+
+# ---- the same three products as ONE bf16 pass (the "bf16_train" mode of the encoders) ----
+def linear_fwd_bf16(x, w, b, out, M, N, K, **kw):
+    """out[M,N] = x[M,K] @ w[N,K]^T + b (+ fused training epilogue); x, w: single bf16 planes (or Planes: their hi plane)."""
+    return ops.gemm_bf16_train(x, w, out, M, N, K, bias=b, **kw)
+
+
+def linear_dgrad_bf16(dy, w_t, out, M, N_in, N_out, **kw):
+    """out[M,N_in] = dy[M,N_out] @ w[N_out,N_in], as the NT product on w_t = the plane of w^T [N_in, N_out] (ops.split_planes_t)."""
+    return ops.gemm_bf16_train(dy, w_t, out, M, N_in, N_out, **kw)
+
+
+def linear_wgrad_bf16(ws, dy, x, dw, db, M, N_in, N_out):
+    """dw[N_out,N_in] = dy[M,N_out]^T @ x[M,N_in];  db[N_out] = colsum(bf16(dy)) from the same call (the 256 x 256 TN kernel sums the
+    fragments it stages; the general family is followed by a column-sum pass over the plane)."""
+    bm, sp = ops.bf16_train_tn_tiling(N_out, N_in, M)
+    skw = ws.vec("splitk", sp * N_out * N_in) if sp > 1 else None
+    cs_ws = ws.vec("colsum_gemm", max(128, sp * ((N_in + 255) // 256)) * N_out) if db is not None else None
+    ops.gemm_bf16_train(dy, x, dw, N_out, N_in, M, trans=True, splitk_ws=skw, splits=sp, block_m=bm, colsum=db, colsum_ws=cs_ws)
 
 
 def _ln_bwd(ws, dy, x, gamma, mean, rstd, dx, dgamma, dbeta, rows, D, **kw):

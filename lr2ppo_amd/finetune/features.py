@@ -158,12 +158,14 @@ class FeatureExtractor(nn.Module):
     (TransformerEncoder._forward_train_fp8 / _backward_train_fp8) on every route, extract() included (that forward, dropout off) --
     or "bf16" (BASELINE.json configs[2]'s literal dtype): extract() / no-grad forward() run every projection and the attention
     of both stacks as ONE bf16 pass over single-plane activations (TransformerEncoder.forward_bf16); inference only, like "mxfp8",
-    ten times closer to the parity path than it.
+    ten times closer to the parity path than it -- or "bf16_train": fine-tuning in single-pass bf16, every projection's forward, input
+    gradient and weight gradient ONE bf16 pass with fp32 accumulation, fp32 residual stream and fp32 master weights
+    (TransformerEncoder._forward_train_bf16 / _backward_train_bf16) on every route, extract() included.
     recompute: the training forwards of both towers keep each layer's input only and the backward re-runs a layer's forward right
     before that layer's backward (TransformerEncoder.recompute): the same bits, ~1/12 of the activation memory, one more
     forward per step.  Embeddings, the projection and the heads keep their activations."""
 
-    PRECISIONS = ("split_bf16", "mxfp8", "mxfp8_train", "bf16")
+    PRECISIONS = ("split_bf16", "mxfp8", "mxfp8_train", "bf16", "bf16_train")
     INFERENCE_ONLY = ("mxfp8", "bf16")
 
     def __init__(self, vit_args: Optional[argparse.Namespace] = None, text_args: Optional[argparse.Namespace] = None,
@@ -188,6 +190,7 @@ class FeatureExtractor(nn.Module):
                                   if self.vit_args.hidden_size != self.feat_dim else None)
         self.text.embedding.defer_id_check = True          # one check per extract() at its end, not one sync per call
         self.image.encoder.fp8_train = self.text.encoder.fp8_train = precision == "mxfp8_train"
+        self.image.encoder.bf16_train = self.text.encoder.bf16_train = precision == "bf16_train"
         self.image.encoder.recompute = self.text.encoder.recompute = self.recompute
 
     def saved_activation_bytes(self, frames_shape, ids_shape) -> int:
@@ -238,7 +241,7 @@ class FeatureExtractor(nn.Module):
         if self.training or (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())):
             raise NotImplementedError(f"FeatureExtractor(precision='{self.precision}') is an inference mode (frozen feature "
                                       "extraction: extract(), or eval() under torch.no_grad()); train the encoders in "
-                                      "'split_bf16' or 'mxfp8_train'")
+                                      "'split_bf16', 'bf16_train' or 'mxfp8_train'")
         return "forward_fp8" if self.precision == "mxfp8" else "forward_bf16"
 
     def text_features(self, ids: torch.Tensor, seg: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -303,7 +306,7 @@ class FeatureExtractor(nn.Module):
         if not frames.is_cuda or not ids.is_cuda:
             raise TypeError("lr2ppo_amd: frames / ids must live on the HIP device (no CPU path)")
         if self.precision in self.INFERENCE_ONLY:
-            raise NotImplementedError(f"forward_train: the encoders train in 'split_bf16' or 'mxfp8_train' (precision="
+            raise NotImplementedError(f"forward_train: the encoders train in 'split_bf16', 'bf16_train' or 'mxfp8_train' (precision="
                                       f"'{self.precision}' is inference only)")
         B, n_img = frames.shape[:2]
         T, L = ids.shape[1:]
@@ -442,6 +445,9 @@ def raw_input_opts(parser):
     parser.add_argument("--fp8_finetune", action="store_true",
                         help="with --raw_inputs --finetune_encoders: train both stacks with MX-FP8 products forward and backward "
                              "(FeatureExtractor(precision='mxfp8_train'))")
+    parser.add_argument("--bf16_finetune", action="store_true",
+                        help="with --raw_inputs --finetune_encoders: train both stacks with ONE bf16 pass per product, forward and "
+                             "backward, fp32 accumulation and fp32 master weights (FeatureExtractor(precision='bf16_train'))")
     parser.add_argument("--recompute_activations", action="store_true",
                         help="with --finetune_encoders: keep one layer's activations at a time (each layer's forward runs again "
                              "in front of its backward: same gradients, ~1/12 of the activation memory, one more forward per step)")
@@ -463,10 +469,16 @@ def build_extractor(args, num_tasks: int = 1, trainable: bool = False) -> Featur
                          "--finetune_encoders and --fp8_finetune")
     if fp8_train and not trainable:
         raise ValueError("--fp8_finetune trains the encoders in MX-FP8: it needs --finetune_encoders")
+    bf16_train = bool(getattr(args, "bf16_finetune", False))
+    if bf16_train and not trainable:
+        raise ValueError("--bf16_finetune trains the encoders in single-pass bf16: it needs --finetune_encoders")
+    if bf16_train and (fp8_train or fp8 or bf16):
+        raise ValueError("--bf16_finetune excludes --fp8_finetune, --fp8_features and --bf16_features")
     recompute = bool(getattr(args, "recompute_activations", False))
     if recompute and not trainable:
         raise ValueError("--recompute_activations is a training-memory switch: it needs --finetune_encoders")
-    precision = "mxfp8" if fp8 else ("bf16" if bf16 else ("mxfp8_train" if fp8_train else "split_bf16"))
+    precision = "mxfp8" if fp8 else ("bf16" if bf16 else ("mxfp8_train" if fp8_train else
+                                                               ("bf16_train" if bf16_train else "split_bf16")))
     fx = FeatureExtractor(encoder_args(IMAGE_TOWERS.get(tower, tower), **over), encoder_args(TEXT_CONFIG, **over),
                           seq_length=args.seq_length, feat_dim=args.visual_feat_dim, precision=precision,
                           recompute=recompute)

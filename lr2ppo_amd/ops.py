@@ -5,6 +5,7 @@ current HIP stream to the native library.  All tensors are fp32, contiguous, on 
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import functools
 import os
@@ -312,6 +313,12 @@ def choose_tiling(M: int, N: int, K: int, trans_a: bool, trans_b: bool = False):
         sp256 = _gemm256_tn_splits(M, N, K, _PASSES)
         if sp256:
             return 256, sp256    # planes x planes only, as above
+    return _general_tiling(M, N, K, trans_a, trans_b)
+
+
+@functools.lru_cache(maxsize=4096)
+def _general_tiling(M: int, N: int, K: int, trans_a: bool, trans_b: bool):
+    """choose_tiling's answer for the 128- / 64-row kernel family alone."""
     bm = 64 if (M <= 64 and not trans_a) else 128
     tiles = ((M + bm - 1) // bm) * ((N + 127) // 128)
     if bm == 128 and not trans_a and not trans_b and tiles < 1536:
@@ -515,6 +522,125 @@ def gemm_bf16_launch_counts():
     c = (C.c_uint64 * 2)()
     _nat.check(_nat.lib().lr2_gemm_bf16_launch_counts(c), "lr2_gemm_bf16_launch_counts")
     return int(c[0]), int(c[1])
+
+
+# ---- single-pass bf16 products of encoder training (the "bf16_train" mode) --------------------------------------------
+_BF16_TRAIN_FORCE_256 = False
+
+
+@contextlib.contextmanager
+def bf16_train_force_256():
+    """Tests: inside the block every product of gemm_bf16_train that names no block_m goes to the 256 x 256 single-pass kernels,
+    whatever its size (the encoder stacks of the tests are too small for the dispatch rule to send anything there)."""
+    global _BF16_TRAIN_FORCE_256
+    prev, _BF16_TRAIN_FORCE_256 = _BF16_TRAIN_FORCE_256, True
+    try:
+        yield
+    finally:
+        _BF16_TRAIN_FORCE_256 = prev
+
+
+@functools.lru_cache(maxsize=4096)
+def gemm256_tn_b1_splits(M: int, N: int, K: int) -> int:
+    """K-split count when the single-pass weight gradient C[M, N] = A[K, M]^T B[K, N] should run on the 256 x 256 TN kernel
+    (csrc/gemm256_tn_b1.hip), else 0 (the 128-row family at passes = 1).  _gemm256_tn_splits' rule for the 3-pass kernel -- few output
+    tiles, a long contraction, tiles x splits in ONE round of the 256 CUs -- with K steps of 64 rows, at least 8 of them per workgroup.
+    Fitted to tools/gemm_bench.py --bf16 --tn on MI355X, bias gradient included (us; this kernel at the rule's splits / the 128-row family
+    at passes = 1 + its column-sum pass / the 3-pass 256 x 256 TN kernel), (N_out, N_in):
+      T = 100864: (768, 3072) 553 / 724 / 1081;  (3072, 768) 490 / 773 / 1084;  (2304, 768) 377 / 620 / 824;  (768, 768) 146 / 248 / 296
+      T = 12544:  (768, 3072) 85 / 98 / 149;     (3072, 768) 88 / 100 / 152;    (2304, 768) 74 / 78 / 122;    (768, 768) 43 / 46 / 60
+    and to --bm 256 --splits {3, 4, 7, 9, 14, 18, 28, 56}: one full round is the optimum on every shape (36 tiles: 7 splits 554 us, 4
+    694, 14 583; 27 tiles: 9 splits 385, 7 433, 18 407; 9 tiles: 28 splits 137, 14 208, 56 169; at T = 12544 24 splits 43, 14 46).
+    -> the kernel wins all eight shapes; the rule is the 3-pass kernel's."""
+    if K < 4096:
+        return 0
+    tiles = ((M + 255) // 256) * ((N + 255) // 256)
+    if tiles > 128 or M * N < 0.85 * tiles * 65536:
+        return 0
+    steps = (K + 63) // 64
+    return max(1, min(256 // tiles, steps // 8))
+
+
+def bf16_train_tn_tiling(M: int, N: int, K: int):
+    """(block_m, splits) of a single-pass weight gradient: the 256 x 256 TN kernel by gemm256_tn_b1_splits, else the general family."""
+    sp = gemm256_tn_b1_splits(M, N, K)
+    if _BF16_TRAIN_FORCE_256:
+        return 256, max(1, sp)
+    return (256, sp) if sp else _general_tiling(M, N, K, True, True)
+
+
+def _one_plane(t, numel: int, what: str):
+    """A single bf16 plane as (pointer, elements addressable): a 2-byte HIP tensor, or the hi plane (= bf16(x)) of a Planes matrix."""
+    if isinstance(t, Planes):
+        t = t.buf[:t.rows * t.cols]
+    return _plane_ptr(t, numel, what), t.numel()
+
+
+def gemm_bf16_train(a, b, out: Optional[torch.Tensor], M: int, N: int, K: int, *, trans: bool = False, lda: Optional[int] = None,
+                    ldb: Optional[int] = None, ld_out: Optional[int] = None, bias: Optional[torch.Tensor] = None, act: int = 0,
+                    out_z: Optional[torch.Tensor] = None, aux_z: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None,
+                    drop: Optional[Drop] = None, accumulate: bool = False, alpha: float = 1.0, out_plane: Optional[torch.Tensor] = None,
+                    out_planes: Optional[Planes] = None, splitk_ws: Optional[torch.Tensor] = None, splits: Optional[int] = None,
+                    block_m: Optional[int] = None, colsum: Optional[torch.Tensor] = None, colsum_ws: Optional[torch.Tensor] = None):
+    """One bf16 pass with the training epilogue (lr2_gemm_bf16_train); a, b: single bf16 planes (2-byte HIP tensors; a Planes matrix
+    contributes its hi plane).  NOT the parity path.
+    trans=False: out[M, N] = a[M, K] @ b[N, K]^T -- alpha, bias, act 0 / 1 (GELU, out_z keeps the pre-activation) / 2 (x GELU'(aux_z)),
+      drop, resid, accumulate -> `out` (fp32) and / or ONE plane `out_plane` or hi / lo `out_planes`.  block_m None: use_gemm256_b1.
+    trans=True: out[M, N] = a[K, M]^T @ b[K, N] (the weight gradient; K = token rows, any count) -> `out`; colsum [M] receives the column
+      sums of a (the bias gradient, of the bf16 plane as the product sees it).  block_m / splits None: bf16_train_tn_tiling."""
+    _chk_f32(out, bias, out_z, aux_z, resid, colsum, colsum_ws)
+    if lda is None:
+        lda = M if trans else K
+    if ldb is None:
+        ldb = N if trans else K
+    if trans:
+        a_ptr, _ = _one_plane(a, (K - 1) * lda + M, "gemm_bf16_train: a")
+        b_ptr, _ = _one_plane(b, (K - 1) * ldb + N, "gemm_bf16_train: b")
+        a_n, b_n = (K - 1) * lda + M, (K - 1) * ldb + N             # the EXACT extents: rows >= K read as zero
+        if block_m is None or splits is None:
+            bm, sp = bf16_train_tn_tiling(M, N, K)
+            block_m = bm if block_m is None else block_m
+            splits = sp if splits is None else splits
+    else:
+        a_ptr, a_n = _one_plane(a, (M - 1) * lda + K, "gemm_bf16_train: a")
+        b_ptr, b_n = _one_plane(b, (N - 1) * ldb + K, "gemm_bf16_train: b")
+        if block_m is None:
+            block_m = 256 if (_BF16_TRAIN_FORCE_256 or use_gemm256_b1(M, N, K)) else _bf16_fallback_block_m(M, N)
+        splits = 1 if splits is None else splits
+    if splits > 1 and (splitk_ws is None or splitk_ws.numel() < splits * M * N):
+        raise ValueError(f"split-K workspace too small: need {splits * M * N} floats")
+    if out_plane is not None and out_planes is not None:
+        raise ValueError("gemm_bf16_train: out_plane excludes out_planes")
+    e = _nat.Epilogue()
+    e.bias, e.resid, e.aux_z, e.out, e.out_z = _ptr(bias), _ptr(resid), _ptr(aux_z), _ptr(out), _ptr(out_z)
+    e.ld_resid, e.ld_aux, e.ld_out, e.ld_z = _ld(resid, N), _ld(aux_z, N), (N if ld_out is None else ld_out), _ld(out_z, N)
+    if out_plane is not None:
+        e.out_hi, e.out_lo_off, e.ld_planes = _plane_ptr(out_plane, M * N, "gemm_bf16_train: out_plane"), 0, N
+    elif out_planes is not None:
+        if out_planes.rows != M or out_planes.cols != N:
+            raise ValueError("gemm_bf16_train: out_planes must be [M, N]")
+        e.out_hi, e.out_lo_off, e.ld_planes = out_planes.data_ptr(), out_planes.lo_off, N
+    e.act, e.accumulate, e.alpha = act, 1 if accumulate else 0, alpha
+    if drop is not None and drop.p > 0.0:
+        e.drop_p, e.drop_seed, e.drop_site, e.drop_seed_dev = drop.p, drop.seed, drop.site, drop.seed_dev_ptr()
+    if colsum is not None:
+        if not trans or colsum.numel() != M or colsum_ws is None or colsum_ws.numel() < max(128, splits * ((N + 255) // 256)) * M:
+            raise ValueError("gemm_bf16_train(colsum=...): trans=True only; colsum [M], colsum_ws >= max(128, splits * ceil(N / 256)) * M floats")
+        e.colsum, e.colsum_ws = colsum.data_ptr(), colsum_ws.data_ptr()
+    t = 1 if trans else 0
+    with _Timed(f"gemm_bf16t_{'TN' if trans else 'NT'}_M{M}_N{N}_K{K}", 2.0 * M * N * K, 2.0 * (M * K + N * K) + 4.0 * M * N):
+        rc = _nat.lib().lr2_gemm_bf16_train(a_ptr, b_ptr, M, N, K, lda, ldb, t, t, a_n * 2, b_n * 2, C.byref(e), _ptr(splitk_ws),
+                                            splits, block_m, _stream())
+    if rc:
+        _nat.check(rc, f"lr2_gemm_bf16_train(M={M},N={N},K={K},trans={trans},block_m={block_m},splits={splits})")
+    return out if out is not None else (out_plane if out_plane is not None else out_planes)
+
+
+def gemm_bf16_train_launch_counts():
+    """(256 x 256 NT kernel, 256 x 256 TN kernel, general family) launches by gemm_bf16_train since the library was loaded."""
+    c = (C.c_uint64 * 3)()
+    _nat.check(_nat.lib().lr2_gemm_bf16_train_launch_counts(c), "lr2_gemm_bf16_train_launch_counts")
+    return int(c[0]), int(c[1]), int(c[2])
 
 
 # workgroups of the LayerNorm backward (each leaves one partial row of d gamma / d beta): 4 per CU.  With one per CU (round 2) the

@@ -127,6 +127,9 @@ class _Kept:
     def planes(self, name, rows, cols):
         return self.arena.planes(rows, cols) if self.arena is not None else ops.Planes.empty(rows, cols, self.dev)
 
+    def plane(self, name, rows, cols):                                   # ONE bf16 plane (the bf16_train mode)
+        return self.arena.plane(rows, cols) if self.arena is not None else torch.empty(rows * cols, dtype=torch.int16, device=self.dev)
+
     def mx_t(self, name, rows, cols):
         return None                                                      # quant_mxfp8_t allocates the column-blocked copy
 
@@ -150,6 +153,9 @@ class _Reused:
     def planes(self, name, rows, cols):
         return self.enc._ws.planes(self.prefix + name, rows, cols)
 
+    def plane(self, name, rows, cols):
+        return self.enc._ws.plane(self.prefix + name, rows, cols)
+
     def mx_t(self, name, rows, cols):
         return self.enc._mx(self.prefix + name, rows, cols, self.dev)
 
@@ -161,6 +167,9 @@ class TransformerEncoder(nn.Module):
     # True: the training forward keeps each layer's INPUT only; the backward re-runs layer i's forward (same dropout seed and sites, same
     # weight operands: the same bits) into reused workspace buffers right before layer i's backward
     recompute = False
+    # True: the training schedule (and every forward) runs the four projections of every layer as ONE bf16 pass, forward, input gradient
+    # and weight gradient (_forward_train_bf16 / _backward_train_bf16; FeatureExtractor(precision="bf16_train"))
+    bf16_train = False
 
     def __init__(self, args):
         super().__init__()
@@ -204,6 +213,8 @@ class TransformerEncoder(nn.Module):
             return _EncoderFn.apply(self, emb, seg, *list(self.parameters()))
         if self.fp8_train:
             return self._forward_train_fp8(emb, seg, save=False)[0]      # no backward follows: nothing kept, no x^T written
+        if self.bf16_train:
+            return self._forward_train_bf16(emb, seg, save=False)[0]
         if self.training and any(l.dropout_1.p > 0 for l in self.transformer):
             out, _ = self._forward_train(emb, seg)       # dropout without a graph (torch.no_grad() in train mode)
             return out
@@ -215,7 +226,7 @@ class TransformerEncoder(nn.Module):
         its keys and values for every row but its query, output projection and feed-forward for row 0 only: 5/6 of that
         layer's matrix work is never consumed and is not computed.  With gradients enabled: the full forward, sliced."""
         needs_grad = torch.is_grad_enabled() and (emb.requires_grad or any(p.requires_grad for p in self.parameters()))
-        if needs_grad or self.fp8_train or (self.training and any(l.dropout_1.p > 0 for l in self.transformer)):
+        if needs_grad or self.fp8_train or self.bf16_train or (self.training and any(l.dropout_1.p > 0 for l in self.transformer)):
             return self.forward(emb, seg)[:, 0, :]
         if emb.dtype != torch.float32 or not emb.is_cuda:
             raise TypeError("lr2ppo_amd: emb must be a float32 tensor on the HIP device (no CPU path)")
@@ -500,6 +511,10 @@ class TransformerEncoder(nn.Module):
         pre = self.layernorm_positioning == "pre"
         if recompute:                                                   # each layer's output = the next one's input (256: alignment)
             return 4 * M * E + 256, (8 * M + 8 * 256 if self.final_layernorm else 0)
+        if self.bf16_train:
+            # the split-bf16 list below with the LayerNorm outputs (x_p, x2_p / inter_p: 2 x M x E each) and GELU(z) (2 x M x F) kept as
+            # ONE bf16 plane instead of hi / lo planes: 4 M E + 2 M F bytes less per layer, either placement
+            return (28 if pre else 36) * M * E + 6 * M * F + 16 * M + 4 * B * H * L + 20 * 256, 4 * M * E + 8 * M + 8 * 256
         if self.fp8_train:
             Mp = -(-M // 128) * 128                                     # x^T, o^T, x2^T [E, Mp] and GELU(z)^T [F, Mp]: bytes + scale bytes
             return ((24 if pre else 32) * M * E + 4 * M * F + 16 * M + 4 * B * H * L + (3 * E + F) * (Mp + Mp // 32),
@@ -569,6 +584,8 @@ class TransformerEncoder(nn.Module):
     def _forward_train(self, emb, seg):
         if self.fp8_train:
             return self._forward_train_fp8(emb, seg)
+        if self.bf16_train:
+            return self._forward_train_bf16(emb, seg)
         dims = B, L, E, H, hd, M, F = self._dims(emb)
         dev = emb.device
         if self._ws is None or self._ws.device != dev:
@@ -642,6 +659,8 @@ class TransformerEncoder(nn.Module):
         into these tensors (grad_buffers()) instead of a fresh allocation."""
         if saved.get("fp8"):
             return self._backward_train_fp8(saved, dout, G)
+        if saved.get("bf16"):
+            return self._backward_train_bf16(saved, dout, G)
         B, L, E, H, hd, M, F = saved["dims"]
         dev, seg, W = dout.device, saved["seg"], saved["W"]
         ws = self._ws
@@ -974,6 +993,210 @@ class TransformerEncoder(nn.Module):
                 dff_ready = nxt
             else:
                 ops.gemm_mxfp8(a, w["wqkv_t"], dprev, resid=d_t1)
+            dh = dprev
+            saved["layers"][i] = None
+        return dh.view(B, L, E), G
+
+    # ---- single-pass bf16 training schedule (FeatureExtractor(precision="bf16_train")) -----------------------------------
+    # _forward_train / _backward_train in the same order, with the same dropout sites, `saved` / G contract and gradient layout, but every
+    # projection -- forward, input gradient, weight gradient -- ONE bf16 pass with fp32 accumulation (ops.gemm_bf16_train:
+    # csrc/gemm256_b1.hip, csrc/gemm256_tn_b1.hip, the 128- / 64-row family at passes = 1).  The attention (3-pass planes kernels on hi / lo
+    # qkv_p, o_p, do_p, dqkv_p), every LayerNorm, the fp32 residual stream and the fp32 master weights stay as they are.  An activation
+    # that only feeds products (LayerNorm outputs, GELU(z)) is kept as ONE plane; a product reads the hi plane (= bf16(x)) of a tensor
+    # that exists as hi / lo planes for another reader.
+    def _bf16_train_weights(self, dev):
+        """Per layer: the hi planes of _weight_planes (forward: B = bf16(W) [out, in]) and of their split_planes_t transposes (input
+        gradient: B = bf16(W^T) [in, out]); re-split when a parameter was written."""
+        W = self._weight_planes(dev)
+        sig = (dev,) + tuple((p.data_ptr(), p._version, ops.param_write_count(p)) for p in self.parameters())
+        if getattr(self, "_bf16t_sig", None) != sig:
+            out = []
+            for layer, w in zip(self.transformer, W):
+                att, ffn = layer.self_attn, layer.feed_forward
+                E, F = att.final_linear.out_features, ffn.linear_1.out_features
+                ent = {"bqkv": w["bqkv"]}
+                for k in ("wqkv", "wo", "w1", "w2"):
+                    ent[k] = w[k].buf[:w[k].rows * w[k].cols]
+                ent["wqkv_t"], ent["w1_t"] = w["wqkv_t"], w["w1_t"]
+                ent["wo_t"] = ops.split_planes_t(att.final_linear.weight.data.contiguous(), ops.Planes.empty(E, E, dev))
+                ent["w2_t"] = ops.split_planes_t(ffn.linear_2.weight.data.contiguous(), ops.Planes.empty(F, E, dev))
+                out.append(ent)
+            self._bf16t_w, self._bf16t_sig = out, sig
+            self.bf16_weight_splits = getattr(self, "bf16_weight_splits", 0) + 1
+        return self._bf16t_w
+
+    def _layer_fwd_train_bf16(self, i, w, h, h_b, A, seg, dims, drop):
+        """Layer i of the bf16 training schedule.  h: the layer's input [M, E] (fp32); h_b: its bf16 plane (post-LN; None for pre-LN);
+        A: the allocator of everything the layer writes.  -> (S: what the backward reads, the layer's output, its plane (post-LN) or None)."""
+        B, L, E, H, hd, M, F = dims
+        layer = self.transformer[i]
+        att, ffn = layer.self_attn, layer.feed_forward
+        ln1, ln2 = layer.layer_norm_1, layer.layer_norm_2
+        pre = self.layernorm_positioning == "pre"
+        scale = 1.0 / math.sqrt(float(hd))
+        mat, vec, pl, p1 = A.mat, A.vec, A.planes, A.plane
+        fwd = engine.linear_fwd_bf16
+        s0 = 4 * i
+        S = {}
+        if pre:
+            x_b, S["m1"], S["r1"], S["h_in"] = p1("x_b", M, E), vec("m1", M), vec("r1", M), h
+            ops.layernorm_fwd(h, ln1.gamma.data, ln1.beta.data, None, S["m1"], S["r1"], rows=M, D=E, eps=ln1.eps, mode=1, out_plane=x_b)
+        else:
+            x_b = h_b
+        qkv_p, o_p, t1 = pl("qkv_p", M, 3 * E), pl("o_p", M, E), mat("t1", M, E)
+        fwd(x_b, w["wqkv"], w["bqkv"], None, M, 3 * E, E, out_planes=qkv_p)          # hi / lo: the 3-pass attention reads both
+        S["lse"] = vec("lse", B * H * L)
+        ops.self_attn_fwd(qkv_p, seg, o_p, batch=B, heads=H, L=L, head_dim=hd, scale=scale, lse=S["lse"], drop=drop(s0))
+        fwd(o_p, w["wo"], att.final_linear.bias.data, t1, M, E, E, resid=h, drop=drop(s0 + 1))
+        z, ff_b = mat("z", M, F), p1("ff_b", M, F)
+        S.update(x_b=x_b, qkv_p=qkv_p, o_p=o_p, t1=t1, z=z, ff_b=ff_b)
+        if pre:
+            x2_b, S["m2"], S["r2"] = p1("x2_b", M, E), vec("m2", M), vec("r2", M)
+            ops.layernorm_fwd(t1, ln2.gamma.data, ln2.beta.data, None, S["m2"], S["r2"], rows=M, D=E, eps=ln2.eps, mode=1, out_plane=x2_b)
+            fwd(x2_b, w["w1"], ffn.linear_1.bias.data, None, M, F, E, act=1, out_z=z, out_plane=ff_b)
+            hn = mat("hn%d" % (i & 1), M, E)                            # reused buffers: the layer output alternates between two
+            fwd(ff_b, w["w2"], ffn.linear_2.bias.data, hn, M, E, F, resid=t1, drop=drop(s0 + 2))
+            S["x2_b"] = x2_b
+            return S, hn, None
+        inter, inter_b, S["m1"], S["r1"] = mat("inter", M, E), p1("inter_b", M, E), vec("m1", M), vec("r1", M)
+        ops.layernorm_fwd(t1, ln1.gamma.data, ln1.beta.data, inter, S["m1"], S["r1"], rows=M, D=E, eps=ln1.eps, mode=1, out_plane=inter_b)
+        fwd(inter_b, w["w1"], ffn.linear_1.bias.data, None, M, F, E, act=1, out_z=z, out_plane=ff_b)
+        t2 = mat("t2", M, E)
+        fwd(ff_b, w["w2"], ffn.linear_2.bias.data, t2, M, E, F, resid=inter, drop=drop(s0 + 2))
+        # (two output-plane buffers by layer parity: see _layer_fwd_train)
+        hn, hn_b, S["m2"], S["r2"] = mat("hn%d" % (i & 1), M, E), p1("h_b%d" % ((i + 1) & 1), M, E), vec("m2", M), vec("r2", M)
+        ops.layernorm_fwd(t2, ln2.gamma.data, ln2.beta.data, hn, S["m2"], S["r2"], rows=M, D=E, eps=ln2.eps, mode=1, out_plane=hn_b)
+        S.update(inter_b=inter_b, t2=t2)
+        return S, hn, hn_b
+
+    def _input_plane(self, h, A, name, M, E):
+        """bf16(h) as ONE plane: the hi plane of a planes split (post-LN: the first layer's, or a recomputed layer's, operand)."""
+        return ops.split_planes(h, A.planes(name, M, E)).buf[:M * E]
+
+    @torch.no_grad()
+    def _forward_train_bf16(self, emb, seg, save: bool = True):
+        """save=False (a forward no backward follows: extract(), eval and rollout forwards): the same arithmetic and the same output
+        bits, with the activations in reused workspace buffers."""
+        dims = B, L, E, H, hd, M, F = self._dims(emb)
+        if E % 64 or F % 64:
+            raise ValueError("bf16_train: hidden and feed-forward widths must be multiples of 64")
+        dev = emb.device
+        if self._ws is None or self._ws.device != dev:
+            self._ws = engine.Workspace(dev)
+        seg = seg.to(device=dev, dtype=torch.int64).contiguous().view(-1)
+        W = self._bf16_train_weights(dev)
+        p = float(self.transformer[0].dropout_1.p) if self.training else 0.0
+        seed = runtime.next_drop(p, 0).seed if p > 0 else 0
+        drop = (lambda site: ops.Drop(p, seed, site)) if p > 0 else (lambda site: None)
+        pre = self.layernorm_positioning == "pre"
+        rc = save and bool(self.recompute)
+        per_layer, tail = self._saved_bytes(B, L, rc)
+        kept = _Kept(dev, engine.Arena(dev, self.layers_num * per_layer + tail)) if save else None
+        A = kept if save and not rc else _Reused(self, dev, "b16:", out=kept if rc else None)
+        h = emb.detach().contiguous().view(M, E)
+        h_b = None if pre else self._input_plane(h, A, "h_p0", M, E)
+        saved = {"bf16": True, "layers": [], "seg": seg, "dims": dims, "drop": (p, seed), "W": W, "recompute": rc}
+        for i, w in enumerate(W):
+            S, hn, hn_b = self._layer_fwd_train_bf16(i, w, h, h_b, A, seg, dims, drop)
+            if save:
+                saved["layers"].append({"h_in": h} if rc else S)
+            h, h_b = hn, hn_b
+        if self.final_layernorm:
+            out = torch.empty(B, L, E, device=dev)
+            fin = kept if save else A
+            mf, rf = fin.vec("mf", M), fin.vec("rf", M)
+            ops.layernorm_fwd(h, self.layer_norm.gamma.data, self.layer_norm.beta.data, out.view(M, E), mf, rf,
+                              rows=M, D=E, eps=self.layer_norm.eps, mode=1)
+            saved["h_final"], saved["mf"], saved["rf"] = h, mf, rf
+        else:
+            out = h.view(B, L, E) if save else h.clone().view(B, L, E)      # not a view of a reused workspace buffer
+        return out, (saved if save else None)
+
+    @torch.no_grad()
+    def _backward_train_bf16(self, saved, dout, G=None):
+        """_backward_train for a forward of _forward_train_bf16.  A gradient that a LayerNorm backward or the attention backward wrote
+        as hi / lo planes enters its two products (input gradient: A; weight gradient: A^T, with the bias gradient) as its hi plane."""
+        B, L, E, H, hd, M, F = saved["dims"]
+        dev, seg, W = dout.device, saved["seg"], saved["W"]
+        ws = self._ws
+        p, seed = saved["drop"]
+        drop = (lambda site: ops.Drop(p, seed, site)) if p > 0 else (lambda site: None)
+        mat = lambda name, r, c: ws.mat("bwd:" + name, r, c)            # noqa: E731
+        pl = lambda name, r, c: ws.planes("bwd:" + name, r, c)          # noqa: E731
+        dgrad, wgrad = engine.linear_dgrad_bf16, engine.linear_wgrad_bf16
+        if G is None:
+            G, qkv_blocks = self._grad_layout(torch.empty(sum(q.numel() for q in self.parameters()), device=dev))
+        else:
+            if G is not getattr(self, "_gviews", None):
+                raise ValueError("_backward_train(G=...): pass grad_buffers()")
+            qkv_blocks = self._gqkv
+        partials = ws.vec("ln_partials", ops.LN_BWD_BLOCKS * 2 * E)
+        dsum_ws = ws.vec("attn_dsum", B * H * L)
+        pre = self.layernorm_positioning == "pre"
+        scale = 1.0 / math.sqrt(float(hd))
+        dh = dout.contiguous().view(M, E)
+        if self.final_layernorm:
+            ln = self.layer_norm
+            dnew = mat("dh0", M, E)
+            top = self.layers_num - 1
+            ops.layernorm_bwd(dh, saved["h_final"], ln.gamma.data, saved["mf"], saved["rf"], dnew, partials, G[ln.gamma],
+                              G[ln.beta], rows=M, D=E, mode=1, eps=ln.eps, dx_planes=pl("dff_p", M, E) if pre else None,
+                              drop=drop(4 * top + 2) if pre else None)
+            dh = dnew
+        dff_ready = pre and self.final_layernorm
+        flip = 1
+        rc = _Reused(self, dev, "b16:") if saved.get("recompute") else None
+        for i in reversed(range(self.layers_num)):
+            layer, w, S = self.transformer[i], W[i], saved["layers"][i]
+            if rc is not None:          # the saving forward of this layer alone (see _backward_train): same seed, sites, operands
+                h_in = S["h_in"]
+                h_b = None if pre else self._input_plane(h_in, rc, "h_p%d" % (i & 1), M, E)
+                S = self._layer_fwd_train_bf16(i, w, h_in, h_b, rc, seg, saved["dims"], drop)[0]
+            att, ffn = layer.self_attn, layer.feed_forward
+            ln1, ln2 = layer.layer_norm_1, layer.layer_norm_2
+            s0 = 4 * i
+            dff_p, dz_b = pl("dff_p", M, E), ws.plane("bwd:dz_b", M, F)
+            if pre:
+                if not dff_ready:
+                    ops.dropout_planes(dh, dff_p, drop(s0 + 2))
+                ffn_in_b = S["x2_b"]
+            else:
+                d_t2 = mat("d_t2", M, E)
+                ops.layernorm_bwd(dh, S["t2"], ln2.gamma.data, S["m2"], S["r2"], d_t2, partials, G[ln2.gamma], G[ln2.beta],
+                                  rows=M, D=E, dx_planes=dff_p, drop=drop(s0 + 2), mode=1, eps=ln2.eps)
+                ffn_in_b = S["inter_b"]
+            wgrad(ws, dff_p, S["ff_b"], G[ffn.linear_2.weight], G[ffn.linear_2.bias], M, F, E)
+            dgrad(dff_p, w["w2_t"], None, M, F, E, act=2, aux_z=S["z"], out_plane=dz_b)
+            wgrad(ws, dz_b, ffn_in_b, G[ffn.linear_1.weight], G[ffn.linear_1.bias], M, E, F)
+            d_t1, dao_p = mat("d_t1", M, E), pl("dao_p", M, E)
+            if pre:
+                d_x2 = mat("d_x2", M, E)
+                dgrad(dz_b, w["w1_t"], d_x2, M, E, F)
+                ops.layernorm_bwd(d_x2, S["t1"], ln2.gamma.data, S["m2"], S["r2"], d_t1, partials, G[ln2.gamma], G[ln2.beta],
+                                  rows=M, D=E, resid_grad=dh, dx_planes=dao_p, drop=drop(s0 + 1), mode=1, eps=ln2.eps)
+            else:
+                d_inter = mat("d_x2", M, E)
+                dgrad(dz_b, w["w1_t"], d_inter, M, E, F, resid=d_t2)
+                ops.layernorm_bwd(d_inter, S["t1"], ln1.gamma.data, S["m1"], S["r1"], d_t1, partials, G[ln1.gamma], G[ln1.beta],
+                                  rows=M, D=E, dx_planes=dao_p, drop=drop(s0 + 1), mode=1, eps=ln1.eps)
+            wgrad(ws, dao_p, S["o_p"], G[att.final_linear.weight], G[att.final_linear.bias], M, E, E)
+            do_p, dqkv_p = pl("do_p", M, E), pl("dqkv_p", M, 3 * E)
+            dgrad(dao_p, w["wo_t"], None, M, E, E, out_planes=do_p)
+            ops.self_attn_bwd(S["qkv_p"], do_p, seg, dqkv_p, S["lse"], dsum_ws, batch=B, heads=H, L=L, head_dim=hd, scale=scale,
+                              drop=drop(s0), o=S["o_p"])
+            wgrad(ws, dqkv_p, S["x_b"], qkv_blocks[i][0], qkv_blocks[i][1], M, E, 3 * E)     # = the three gradients
+            dprev = torch.empty(M, E, device=dev) if i == 0 else mat("dh%d" % flip, M, E)
+            flip ^= 1
+            if pre:
+                d_x1 = mat("d_x1", M, E)
+                dgrad(dqkv_p, w["wqkv_t"], d_x1, M, E, 3 * E)
+                nxt = i > 0
+                ops.layernorm_bwd(d_x1, S["h_in"], ln1.gamma.data, S["m1"], S["r1"], dprev, partials, G[ln1.gamma], G[ln1.beta],
+                                  rows=M, D=E, resid_grad=d_t1, mode=1, eps=ln1.eps, dx_planes=dff_p if nxt else None,
+                                  drop=drop(s0 - 4 + 2) if nxt else None)
+                dff_ready = nxt
+            else:
+                dgrad(dqkv_p, w["wqkv_t"], dprev, M, E, 3 * E, resid=d_t1)
             dh = dprev
             saved["layers"][i] = None
         return dh.view(B, L, E), G

@@ -1,7 +1,7 @@
 """Dual-encoder forward micro-benchmark (ViT-B/16 + RoBERTa-base, random weights, batch 32 of the repo's default shapes).
 Prints ms per forward, algorithmic TFLOP/s (2MNK of the GEMMs + 4 L^2 d of attention) and a per-kernel-class breakdown
 from HIP events.  python tools/encoder_bench.py [--batch 32] [--iters 10] [--passes 3]
---train [--precision mxfp8_train] [--recompute]: forward + backward per step, and the step's peak device memory."""
+--train [--precision mxfp8_train | bf16_train] [--recompute]: forward + backward per step, and the step's peak device memory."""
 import argparse
 import os
 import sys
@@ -89,8 +89,8 @@ def main():
     ap.add_argument("--detail", action="store_true", help="per-signature launch averages")
     ap.add_argument("--train", action="store_true", help="time forward + backward (train mode, dropout 0.1) instead; with "
                     "--ppo-shapes: both towers at the PPO sizes (ViT over batch*16 frames, RoBERTa over batch*2 sequences)")
-    ap.add_argument("--precision", choices=("split_bf16", "mxfp8_train", "bf16", "mxfp8"), default="split_bf16",
-                    help="--train: the encoders' training precision (TransformerEncoder.fp8_train: split_bf16 | mxfp8_train); "
+    ap.add_argument("--precision", choices=("split_bf16", "mxfp8_train", "bf16_train", "bf16", "mxfp8"), default="split_bf16",
+                    help="--train: the encoders' training precision (split_bf16 | mxfp8_train | bf16_train); "
                          "--ppo-shapes without --train: the inference precision (split_bf16 | bf16 | mxfp8)")
     ap.add_argument("--recompute", action="store_true",
                     help="--train: keep each layer's input only and re-run a layer's forward in front of its backward "
@@ -98,6 +98,8 @@ def main():
     a = ap.parse_args()
     if a.recompute and not a.train:
         ap.error("--recompute is a switch of the training schedule: give --train")
+    if a.precision == "bf16_train" and not a.train:
+        ap.error("--precision bf16_train is a training precision: give --train")
     if a.precision in ("bf16", "mxfp8") and (a.train or not a.ppo_shapes):
         ap.error("--precision bf16 / mxfp8 are inference modes: give --ppo-shapes, not --train")
     dev = torch.device("cuda:0")
@@ -117,6 +119,7 @@ def main():
         enc = enc.to(dev)
         enc = enc.train() if a.train else enc.eval()
         enc.fp8_train = a.train and a.precision == "mxfp8_train"
+        enc.bf16_train = a.train and a.precision == "bf16_train"
         enc.recompute = a.recompute
         B = (a.batch * 16 if name.startswith("vit") else a.batch * 2) if a.ppo_shapes else a.batch
         emb = torch.randn(B, L, 768, device=dev, requires_grad=a.train)

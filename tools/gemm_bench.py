@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Micro-benchmark of lr2_gemm on the shapes of the LR2PPO head (run on the GPU box).
 usage: python tools/gemm_bench.py [--passes 3] [--iters 20]
-       python tools/gemm_bench.py --bf16 [--bm 256|128] [--only ...]: the single-pass bf16 product (lr2_gemm_bf16) on the NT shapes"""
+       python tools/gemm_bench.py --bf16 [--bm 256|128] [--only ...]: the single-pass bf16 product (lr2_gemm_bf16) on the NT shapes
+       python tools/gemm_bench.py --bf16 --tn [--bm 256|128] [--splits S] [--only ...]: the single-pass weight gradient
+           (lr2_gemm_bf16_train, TN) on TN_B1_SHAPES, bias gradient included; without --bm each shape is timed on the 256 x 256 TN
+           kernel, on the 128-row family at passes = 1 and on the 3-pass 256 x 256 TN kernel, in that order"""
 import argparse
 import os
 import sys
@@ -32,6 +35,58 @@ SHAPES = [  # (form, M, N, K) as ops.gemm sees them
 ]
 
 
+# (N_out, N_in, T): the encoders' weight gradients over 512 frames x 197 tokens and over 64 sequences x 196 tokens
+TN_B1_SHAPES = [(768, 3072, 100864), (3072, 768, 100864), (2304, 768, 100864), (768, 768, 100864),
+                (768, 3072, 12544), (3072, 768, 12544), (2304, 768, 12544), (768, 768, 12544)]
+
+
+def _time(fn, iters):
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    for _ in range(iters):
+        fn()
+    e.record()
+    torch.cuda.synchronize()
+    return s.elapsed_time(e) / iters
+
+
+def bench_tn_b1(a, dev, g):
+    """dW [N_out, N_in] = dY^T X and db = colsum(dY) as the bf16_train schedule calls them (engine.linear_wgrad_bf16)"""
+    for si, (M, N, K) in enumerate(TN_B1_SHAPES):
+        if a.only is not None and si not in a.only:
+            continue
+        A = torch.randn(K, M, device=dev, generator=g)
+        B = torch.randn(K, N, device=dev, generator=g)
+        Ap, Bp = ops.split_planes(A, ops.Planes.empty(K, M, dev)), ops.split_planes(B, ops.Planes.empty(K, N, dev))
+        out, db = torch.empty(M, N, device=dev), torch.empty(M, device=dev)
+        rule = ops.gemm256_tn_b1_splits(M, N, K)
+        gbm, gsp = ops._general_tiling(M, N, K, True, True)
+        cases = []
+        if a.bm in (None, 256):
+            cases.append(("bf16x1 256x256", 256, a.splits or max(1, rule), 1))
+        if a.bm in (None, 128, 64):
+            cases.append(("bf16x1 general", a.bm or gbm, a.splits or gsp, 1))
+        if a.bm is None:
+            bm3, sp3 = ops.choose_tiling(M, N, K, True, True)
+            cases.append(("split-bf16 x3 ", bm3, sp3, 3))
+        for label, bm, sp, passes in cases:
+            ws = torch.empty(sp * M * N, device=dev) if sp > 1 else None
+            cs_ws = torch.empty(max(128, sp * ((N + 255) // 256)) * M, device=dev)
+            if passes == 1:
+                fn = lambda: ops.gemm_bf16_train(Ap, Bp, out, M, N, K, trans=True, block_m=bm, splits=sp, splitk_ws=ws, colsum=db,  # noqa: E731
+                                                 colsum_ws=cs_ws)
+            else:
+                fn = lambda: ops.gemm(Ap, Bp, out, M, N, K, trans_a=True, trans_b=True, lda=M, ldb=N, splitk_ws=ws, splits=sp,     # noqa: E731
+                                      block_m=bm, passes=3, colsum=db, colsum_ws=cs_ws)
+            ms = _time(fn, a.iters)
+            print(f"{label} TN N_out={M:5d} N_in={N:5d} T={K:6d} bm={bm:3d} splits={sp:3d} (rule {rule:3d}): {ms * 1e3:8.1f} us  "
+                  f"{2.0 * M * N * K / ms / 1e9:7.1f} TFLOP/s", flush=True)
+        del A, B, Ap, Bp, out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--passes", type=int, default=3)
@@ -42,9 +97,14 @@ def main():
     ap.add_argument("--splits", type=int, default=None, help="override split-K factor")
     ap.add_argument("--bf16", action="store_true", help="ONE bf16 plane per operand, one pass (ops.gemm_bf16; NT shapes only); "
                     "--bm 256: the 256 x 256 single-pass kernel, --bm 128: the 128-row family at passes = 1; default: by size")
+    ap.add_argument("--tn", action="store_true", help="with --bf16: the single-pass weight gradient (ops.gemm_bf16_train, TN) on TN_B1_SHAPES")
     a = ap.parse_args()
+    if a.tn and not a.bf16:
+        ap.error("--tn is the weight-gradient form of the single-pass product: give --bf16")
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(0)
+    if a.tn:
+        return bench_tn_b1(a, dev, g)
     for si, (form, M, N, K) in enumerate(SHAPES):
         if a.only is not None and si not in a.only:
             continue
