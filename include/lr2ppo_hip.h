@@ -24,7 +24,7 @@ extern "C" {
 #define LR2_ERR_SHAPE (-2)  /* shape not supported by the kernel's tiling */
 #define LR2_ERR_LAUNCH (-3) /* HIP launch failure */
 
-#define LR2_ABI_VERSION 22
+#define LR2_ABI_VERSION 23
 int lr2_abi_version(void);
 /* Fills name[0..len) with the HIP device name and returns the CU count (or <0). */
 int lr2_device_info(char* name, int len);
@@ -447,6 +447,40 @@ int lr2_gemm_bf16_train(const void* A, const void* B, int M, int N, int K, int l
 /* Diagnostic, as lr2_gemm_bf16_launch_counts: launches issued by lr2_gemm_bf16_train -- counts[0] the 256 x 256 single-pass NT kernel,
  * counts[1] the 256 x 256 single-pass TN kernel, counts[2] the general kernel family. */
 int lr2_gemm_bf16_train_launch_counts(uint64_t counts[3]);
+
+/* ABI 23.  Encoder self-attention of the single-pass bf16 TRAINING mode (FeatureExtractor(precision="bf16_train", bf16_attention=True),
+ * DESIGN 4.6; csrc/selfattn_b1_train.hip): every operand and every output ONE bf16 plane, element (row, h * 64 + d) at
+ * ptr[row * ld + h * 64 + d]; q / k / v are the three column blocks of one [batch * L, 3E] plane, dq / dk / dv likewise; one
+ * v_mfma_f32_16x16x32_bf16 product per tile pair, fp32 softmax, key mask -10000 * (seg <= 0) after the scale.  One workgroup per
+ * (sequence, head) (small batches: up to 4), head_dim 64, 1 <= L <= 288.  NOT the parity path: lr2_self_attn_fwd / lr2_self_attn_bwd
+ * stay the default.
+ *   lr2_self_attn_fwd_bf16_train: lr2_self_attn_fwd_bf16's arithmetic with training's two additions.  The un-normalised probabilities
+ *       p~ = exp2(s - max) are summed in fp32 BEFORE dropout; p~ * (keep ? 1 / (1 - p) : 0) -- lr2_self_attn_fwd's mask stream:
+ *       element ((b * heads + h) * L + q) * pitch(L) + key of (drop_seed, drop_site), pitch = L rounded up to 4 -- is rounded to
+ *       bf16 (nearest even) as the A operand of P V, the accumulator is multiplied by 1 / sum, the context leaves as one bf16 plane
+ *       o_bf16 [batch * L, ld_o].  lse (optional): fp32 [batch, heads, L], the natural-log log-sum-exp of the masked scores (before
+ *       dropout).  drop_p == 0: o_bf16 is byte-equal to lr2_self_attn_fwd_bf16's.
+ *   lr2_self_attn_bwd_bf16: the recomputing backward, two launches.  dQ: S^T = K Q^T, dPd^T = V dO^T, P = softmax, dP = dPd o M,
+ *       D = sum_k dP P, dS = P (dP - D) scale rounded to bf16, dQ = dS K; writes lse_ws and dsum_ws (fp32 [batch, heads, L] each,
+ *       workspaces: the dK / dV launch reads them).  dK / dV: P = exp(S scale + mask - lse), Pd = P o M and dS rounded to bf16,
+ *       dV = Pd^T dO, dK = dS^T Q.  Outputs: round to nearest even of the fp32 accumulators.  Neither the forward's lse nor its
+ *       output is read; the same (drop_p, drop_seed, drop_site) as the forward replays its mask.  No atomics: two calls give the same
+ *       bytes.
+ * LR2_ERR_ARG: a NULL pointer (lse of the forward excepted), q / k / v / d_o not 16-byte or an output not 8-byte aligned, drop_p
+ * outside [0, 1).  LR2_ERR_SHAPE: head_dim != 64, L < 1 or L > 288, a leading dimension that is no multiple of 8 or smaller than
+ * heads * 64.  Nothing is launched by a rejected call.
+ * replaces: tencentpretrain/layers/multi_headed_attn.py:61-74 (scores, mask, softmax, dropout, context) and its autograd, in that
+ * mode. */
+int lr2_self_attn_fwd_bf16_train(const void* q, const void* k, const void* v, int ld, const int64_t* seg, void* o_bf16, int ld_o,
+                                 void* lse, float drop_p, uint64_t drop_seed, uint32_t drop_site, int batch, int heads, int L,
+                                 int head_dim, float scale, void* stream);
+int lr2_self_attn_bwd_bf16(const void* q, const void* k, const void* v, int ld, const void* d_o, int ld_do, const int64_t* seg,
+                           void* dq, void* dk, void* dv, int ld_d, void* lse_ws, void* dsum_ws, float drop_p, uint64_t drop_seed,
+                           uint32_t drop_site, int batch, int heads, int L, int head_dim, float scale, void* stream);
+/* Diagnostic, as lr2_gemm_bf16_launch_counts: counts[0] = accepted lr2_self_attn_fwd_bf16_train calls, counts[1] = accepted
+ * lr2_self_attn_bwd_bf16 calls since the library was loaded.
+ * replaces: nothing (a test hook: which attention a schedule ran; multi_headed_attn.py:61-74 has no counterpart). */
+int lr2_self_attn_bf16_train_launch_counts(uint64_t counts[2]);
 
 /* ABI 20.  MX-FP8 encoder training (FeatureExtractor(precision="mxfp8_train")): the backward's operands, blocked along the axis its
  * products reduce over, and a K-sliced weight-gradient product.

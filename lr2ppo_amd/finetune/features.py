@@ -161,6 +161,8 @@ class FeatureExtractor(nn.Module):
     ten times closer to the parity path than it -- or "bf16_train": fine-tuning in single-pass bf16, every projection's forward, input
     gradient and weight gradient ONE bf16 pass with fp32 accumulation, fp32 residual stream and fp32 master weights
     (TransformerEncoder._forward_train_bf16 / _backward_train_bf16) on every route, extract() included.
+    bf16_attention ("bf16_train" only): the attention core of both towers on ONE bf16 plane per operand as well, forward and backward
+    (TransformerEncoder.bf16_attention: head_dim 64 and L <= 288, other layer shapes keep the 3-pass kernels).
     recompute: the training forwards of both towers keep each layer's input only and the backward re-runs a layer's forward right
     before that layer's backward (TransformerEncoder.recompute): the same bits, ~1/12 of the activation memory, one more
     forward per step.  Embeddings, the projection and the heads keep their activations."""
@@ -170,7 +172,7 @@ class FeatureExtractor(nn.Module):
 
     def __init__(self, vit_args: Optional[argparse.Namespace] = None, text_args: Optional[argparse.Namespace] = None,
                  vocab_size: int = ROBERTA_VOCAB, seq_length: int = 196, feat_dim: Optional[int] = None,
-                 precision: str = "split_bf16", recompute: bool = False):
+                 precision: str = "split_bf16", recompute: bool = False, bf16_attention: bool = False):
         super().__init__()
         self.vit_args = vit_args or encoder_args(VIT_CONFIG)
         self.text_args = text_args or encoder_args(TEXT_CONFIG)
@@ -183,7 +185,9 @@ class FeatureExtractor(nn.Module):
             raise ValueError(f"precision must be one of {self.PRECISIONS}")
         if recompute and precision in self.INFERENCE_ONLY:
             raise ValueError(f"recompute trades time for memory in the TRAINING schedules; precision='{precision}' is inference only")
-        self.precision, self.recompute = precision, bool(recompute)
+        if bf16_attention and precision != "bf16_train":
+            raise ValueError(f"bf16_attention is a switch of precision='bf16_train', not of '{precision}'")
+        self.precision, self.recompute, self.bf16_attention = precision, bool(recompute), bool(bf16_attention)
         self.image = EncoderStack(self.vit_args, vocab_size)
         self.text = EncoderStack(self.text_args, vocab_size)
         self.visual_projection = (VisualProjection(self.vit_args.hidden_size, self.feat_dim)
@@ -192,6 +196,7 @@ class FeatureExtractor(nn.Module):
         self.image.encoder.fp8_train = self.text.encoder.fp8_train = precision == "mxfp8_train"
         self.image.encoder.bf16_train = self.text.encoder.bf16_train = precision == "bf16_train"
         self.image.encoder.recompute = self.text.encoder.recompute = self.recompute
+        self.image.encoder.bf16_attention = self.text.encoder.bf16_attention = self.bf16_attention
 
     def saved_activation_bytes(self, frames_shape, ids_shape) -> int:
         """Bytes of encoder activations forward_train keeps until backward_train for frames [B, n_img, ...] and ids [B, T, L]: the
@@ -448,6 +453,9 @@ def raw_input_opts(parser):
     parser.add_argument("--bf16_finetune", action="store_true",
                         help="with --raw_inputs --finetune_encoders: train both stacks with ONE bf16 pass per product, forward and "
                              "backward, fp32 accumulation and fp32 master weights (FeatureExtractor(precision='bf16_train'))")
+    parser.add_argument("--bf16_attention", action="store_true",
+                        help="with --bf16_finetune: the attention core on ONE bf16 plane per operand too, forward and backward "
+                             "(FeatureExtractor(precision='bf16_train', bf16_attention=True); head_dim 64, sequences up to 288)")
     parser.add_argument("--recompute_activations", action="store_true",
                         help="with --finetune_encoders: keep one layer's activations at a time (each layer's forward runs again "
                              "in front of its backward: same gradients, ~1/12 of the activation memory, one more forward per step)")
@@ -474,6 +482,9 @@ def build_extractor(args, num_tasks: int = 1, trainable: bool = False) -> Featur
         raise ValueError("--bf16_finetune trains the encoders in single-pass bf16: it needs --finetune_encoders")
     if bf16_train and (fp8_train or fp8 or bf16):
         raise ValueError("--bf16_finetune excludes --fp8_finetune, --fp8_features and --bf16_features")
+    bf16_attention = bool(getattr(args, "bf16_attention", False))
+    if bf16_attention and not bf16_train:
+        raise ValueError("--bf16_attention is a switch of the single-pass bf16 training mode: it needs --bf16_finetune")
     recompute = bool(getattr(args, "recompute_activations", False))
     if recompute and not trainable:
         raise ValueError("--recompute_activations is a training-memory switch: it needs --finetune_encoders")
@@ -481,7 +492,7 @@ def build_extractor(args, num_tasks: int = 1, trainable: bool = False) -> Featur
                                                                ("bf16_train" if bf16_train else "split_bf16")))
     fx = FeatureExtractor(encoder_args(IMAGE_TOWERS.get(tower, tower), **over), encoder_args(TEXT_CONFIG, **over),
                           seq_length=args.seq_length, feat_dim=args.visual_feat_dim, precision=precision,
-                          recompute=recompute)
+                          recompute=recompute, bf16_attention=bf16_attention)
     text_path, vit_path = getattr(args, "pretrained_model_path", None), getattr(args, "vit_pretrained_model_path", None)
     if text_path or vit_path:
         if not (text_path and vit_path):

@@ -1120,6 +1120,64 @@ def self_attn_bf16_plan(batch: int, heads: int, L: int, ld: Optional[int] = None
     return bool(f.value)
 
 
+def _attn_plane_args(what: str, seg, batch, heads, L, head_dim, planes):
+    """Checks shared by the two single-plane training attention calls: every (name, tensor, columns) of `planes` is ONE bf16 plane
+    [batch * L, columns]; seg is int64.  Returns E."""
+    E = heads * head_dim
+    if seg.dtype != torch.int64:
+        raise TypeError("seg must be int64")
+    for name, t, cols in planes:
+        _plane_ptr(t, batch * L * cols, f"{what}: {name}")
+    return E
+
+
+def self_attn_fwd_bf16_train(qkv: torch.Tensor, seg, out_plane: torch.Tensor, *, batch, heads, L, head_dim, scale,
+                             lse: Optional[torch.Tensor] = None, drop: Optional[Drop] = None):
+    """Encoder self-attention of the bf16_train mode, forward (lr2_self_attn_fwd_bf16_train).  qkv: ONE bf16 plane [batch * L, 3E] =
+    [Q | K | V] (what gemm_bf16_train(out_plane=...) writes); out_plane: the context as ONE bf16 plane [batch * L, E]; lse: optional
+    fp32 [batch * heads * L]; drop: dropout on the probabilities (self_attn_fwd's mask stream).  head_dim 64, L <= 288."""
+    E = _attn_plane_args("self_attn_fwd_bf16_train", seg, batch, heads, L, head_dim, (("qkv", qkv, 3 * heads * head_dim),
+                                                                                     ("out_plane", out_plane, heads * head_dim)))
+    _chk_f32(lse)
+    if lse is not None and lse.numel() < batch * heads * L:
+        raise ValueError("self_attn_fwd_bf16_train: lse too small")
+    q, k, v = _qkv_ptrs(qkv, E)
+    p, seed, site = (drop.p, drop.seed, drop.site) if drop is not None else (0.0, 0, 0)
+    with _Timed(f"selfattn_b1t_B{batch}_H{heads}_L{L}", 4.0 * batch * heads * L * L * head_dim, 8.0 * batch * L * E):
+        _nat.check(_nat.lib().lr2_self_attn_fwd_bf16_train(q, k, v, 3 * E, seg.data_ptr(), out_plane.data_ptr(), E, _ptr(lse), p, seed,
+                                                           site, batch, heads, L, head_dim, scale, _stream()),
+                   "lr2_self_attn_fwd_bf16_train")
+    return out_plane
+
+
+def self_attn_bwd_bf16(qkv: torch.Tensor, do: torch.Tensor, seg, dqkv: torch.Tensor, lse_ws, dsum_ws, *, batch, heads, L, head_dim,
+                       scale, drop: Optional[Drop] = None):
+    """dQKV (ONE bf16 plane [batch * L, 3E]) from QKV [batch * L, 3E] and dO [batch * L, E] (ONE bf16 plane each) by the recomputing
+    single-plane backward (lr2_self_attn_bwd_bf16); lse_ws / dsum_ws: fp32 [batch * heads * L] scratch.  `drop` as in the forward
+    replays its mask; the forward's output and log-sum-exp are not needed."""
+    E = _attn_plane_args("self_attn_bwd_bf16", seg, batch, heads, L, head_dim, (("qkv", qkv, 3 * heads * head_dim),
+                                                                               ("do", do, heads * head_dim),
+                                                                               ("dqkv", dqkv, 3 * heads * head_dim)))
+    _chk_f32(lse_ws, dsum_ws)
+    if lse_ws.numel() < batch * heads * L or dsum_ws.numel() < batch * heads * L:
+        raise ValueError("self_attn_bwd_bf16: statistics workspaces too small")
+    q, k, v = _qkv_ptrs(qkv, E)
+    dq, dk, dv = _qkv_ptrs(dqkv, E)
+    p, seed, site = (drop.p, drop.seed, drop.site) if drop is not None else (0.0, 0, 0)
+    with _Timed(f"selfattnbwd_b1t_B{batch}_H{heads}_L{L}", 14.0 * batch * heads * L * L * head_dim, 16.0 * batch * L * E):
+        _nat.check(_nat.lib().lr2_self_attn_bwd_bf16(q, k, v, 3 * E, do.data_ptr(), E, seg.data_ptr(), dq, dk, dv, 3 * E,
+                                                     lse_ws.data_ptr(), dsum_ws.data_ptr(), p, seed, site, batch, heads, L, head_dim,
+                                                     scale, _stream()), "lr2_self_attn_bwd_bf16")
+    return dqkv
+
+
+def self_attn_bf16_train_launch_counts():
+    """(forward, backward) calls of the single-plane training attention since the library was loaded."""
+    c = (C.c_uint64 * 2)()
+    _nat.check(_nat.lib().lr2_self_attn_bf16_train_launch_counts(c), "lr2_self_attn_bf16_train_launch_counts")
+    return int(c[0]), int(c[1])
+
+
 def text_embed(src, seg, word, pos, seg_table, out, *, rows, L, D, err: Optional[torch.Tensor] = None):
     """err: optional int32[1] device word; bit 0 / bit 1 are set when a token / segment id is out of range."""
     _chk_f32(word, pos, seg_table, out)

@@ -170,6 +170,10 @@ class TransformerEncoder(nn.Module):
     # True: the training schedule (and every forward) runs the four projections of every layer as ONE bf16 pass, forward, input gradient
     # and weight gradient (_forward_train_bf16 / _backward_train_bf16; FeatureExtractor(precision="bf16_train"))
     bf16_train = False
+    # True (with bf16_train): a layer with head_dim 64 and L <= 288 runs its attention core on ONE bf16 plane per operand, forward and
+    # backward (ops.self_attn_fwd_bf16_train / ops.self_attn_bwd_bf16; FeatureExtractor(..., bf16_attention=True)); every
+    # other layer shape keeps the 3-pass kernels
+    bf16_attention = False
 
     def __init__(self, args):
         super().__init__()
@@ -514,7 +518,11 @@ class TransformerEncoder(nn.Module):
         if self.bf16_train:
             # the split-bf16 list below with the LayerNorm outputs (x_p, x2_p / inter_p: 2 x M x E each) and GELU(z) (2 x M x F) kept as
             # ONE bf16 plane instead of hi / lo planes: 4 M E + 2 M F bytes less per layer, either placement
-            return (28 if pre else 36) * M * E + 6 * M * F + 16 * M + 4 * B * H * L + 20 * 256, 4 * M * E + 8 * M + 8 * 256
+            per_layer = (28 if pre else 36) * M * E + 6 * M * F + 16 * M + 4 * B * H * L + 20 * 256
+            if self._b1_attention(E // H, L):
+                # Q | K | V (6 M E) and the context (2 M E) as ONE plane each, and no log-sum-exp (the backward recomputes it)
+                per_layer -= 8 * M * E + 4 * B * H * L
+            return per_layer, 4 * M * E + 8 * M + 8 * 256
         if self.fp8_train:
             Mp = -(-M // 128) * 128                                     # x^T, o^T, x2^T [E, Mp] and GELU(z)^T [F, Mp]: bytes + scale bytes
             return ((24 if pre else 32) * M * E + 4 * M * F + 16 * M + 4 * B * H * L + (3 * E + F) * (Mp + Mp // 32),
@@ -1001,9 +1009,10 @@ class TransformerEncoder(nn.Module):
     # _forward_train / _backward_train in the same order, with the same dropout sites, `saved` / G contract and gradient layout, but every
     # projection -- forward, input gradient, weight gradient -- ONE bf16 pass with fp32 accumulation (ops.gemm_bf16_train:
     # csrc/gemm256_b1.hip, csrc/gemm256_tn_b1.hip, the 128- / 64-row family at passes = 1).  The attention (3-pass planes kernels on hi / lo
-    # qkv_p, o_p, do_p, dqkv_p), every LayerNorm, the fp32 residual stream and the fp32 master weights stay as they are.  An activation
-    # that only feeds products (LayerNorm outputs, GELU(z)) is kept as ONE plane; a product reads the hi plane (= bf16(x)) of a tensor
-    # that exists as hi / lo planes for another reader.
+    # qkv_p, o_p, do_p, dqkv_p; with bf16_attention and head_dim 64, L <= 288: the single-plane kernels of csrc/selfattn_b1_train.hip
+    # on ONE plane qkv_b, o_b, do_b, dqkv_b each), every LayerNorm, the fp32 residual stream and the fp32 master weights stay as they
+    # are.  An activation that only feeds products (LayerNorm outputs, GELU(z)) is kept as ONE plane; a product reads the hi plane
+    # (= bf16(x)) of a tensor that exists as hi / lo planes for another reader.
     def _bf16_train_weights(self, dev):
         """Per layer: the hi planes of _weight_planes (forward: B = bf16(W) [out, in]) and of their split_planes_t transposes (input
         gradient: B = bf16(W^T) [in, out]); re-split when a parameter was written."""
@@ -1025,6 +1034,10 @@ class TransformerEncoder(nn.Module):
             self.bf16_weight_splits = getattr(self, "bf16_weight_splits", 0) + 1
         return self._bf16t_w
 
+    def _b1_attention(self, hd, L):
+        """Does a bf16_train layer of this shape take the single-plane attention (csrc/selfattn_b1_train.hip)?"""
+        return bool(self.bf16_train and self.bf16_attention and hd == 64 and L <= 288)
+
     def _layer_fwd_train_bf16(self, i, w, h, h_b, A, seg, dims, drop):
         """Layer i of the bf16 training schedule.  h: the layer's input [M, E] (fp32); h_b: its bf16 plane (post-LN; None for pre-LN);
         A: the allocator of everything the layer writes.  -> (S: what the backward reads, the layer's output, its plane (post-LN) or None)."""
@@ -1043,13 +1056,22 @@ class TransformerEncoder(nn.Module):
             ops.layernorm_fwd(h, ln1.gamma.data, ln1.beta.data, None, S["m1"], S["r1"], rows=M, D=E, eps=ln1.eps, mode=1, out_plane=x_b)
         else:
             x_b = h_b
-        qkv_p, o_p, t1 = pl("qkv_p", M, 3 * E), pl("o_p", M, E), mat("t1", M, E)
-        fwd(x_b, w["wqkv"], w["bqkv"], None, M, 3 * E, E, out_planes=qkv_p)          # hi / lo: the 3-pass attention reads both
-        S["lse"] = vec("lse", B * H * L)
-        ops.self_attn_fwd(qkv_p, seg, o_p, batch=B, heads=H, L=L, head_dim=hd, scale=scale, lse=S["lse"], drop=drop(s0))
-        fwd(o_p, w["wo"], att.final_linear.bias.data, t1, M, E, E, resid=h, drop=drop(s0 + 1))
+        if self._b1_attention(hd, L):
+            # ONE plane each for Q | K | V and the context; no log-sum-exp is kept (ops.self_attn_bwd_bf16 recomputes it)
+            qkv_b, o_b, t1 = p1("qkv_b", M, 3 * E), p1("o_b", M, E), mat("t1", M, E)
+            fwd(x_b, w["wqkv"], w["bqkv"], None, M, 3 * E, E, out_plane=qkv_b)
+            ops.self_attn_fwd_bf16_train(qkv_b, seg, o_b, batch=B, heads=H, L=L, head_dim=hd, scale=scale, drop=drop(s0))
+            fwd(o_b, w["wo"], att.final_linear.bias.data, t1, M, E, E, resid=h, drop=drop(s0 + 1))
+            S.update(qkv_b=qkv_b, o_b=o_b)
+        else:
+            qkv_p, o_p, t1 = pl("qkv_p", M, 3 * E), pl("o_p", M, E), mat("t1", M, E)
+            fwd(x_b, w["wqkv"], w["bqkv"], None, M, 3 * E, E, out_planes=qkv_p)          # hi / lo: the 3-pass attention reads both
+            S["lse"] = vec("lse", B * H * L)
+            ops.self_attn_fwd(qkv_p, seg, o_p, batch=B, heads=H, L=L, head_dim=hd, scale=scale, lse=S["lse"], drop=drop(s0))
+            fwd(o_p, w["wo"], att.final_linear.bias.data, t1, M, E, E, resid=h, drop=drop(s0 + 1))
+            S.update(qkv_p=qkv_p, o_p=o_p)
         z, ff_b = mat("z", M, F), p1("ff_b", M, F)
-        S.update(x_b=x_b, qkv_p=qkv_p, o_p=o_p, t1=t1, z=z, ff_b=ff_b)
+        S.update(x_b=x_b, t1=t1, z=z, ff_b=ff_b)
         if pre:
             x2_b, S["m2"], S["r2"] = p1("x2_b", M, E), vec("m2", M), vec("r2", M)
             ops.layernorm_fwd(t1, ln2.gamma.data, ln2.beta.data, None, S["m2"], S["r2"], rows=M, D=E, eps=ln2.eps, mode=1, out_plane=x2_b)
@@ -1179,11 +1201,18 @@ class TransformerEncoder(nn.Module):
                 dgrad(dz_b, w["w1_t"], d_inter, M, E, F, resid=d_t2)
                 ops.layernorm_bwd(d_inter, S["t1"], ln1.gamma.data, S["m1"], S["r1"], d_t1, partials, G[ln1.gamma], G[ln1.beta],
                                   rows=M, D=E, dx_planes=dao_p, drop=drop(s0 + 1), mode=1, eps=ln1.eps)
-            wgrad(ws, dao_p, S["o_p"], G[att.final_linear.weight], G[att.final_linear.bias], M, E, E)
-            do_p, dqkv_p = pl("do_p", M, E), pl("dqkv_p", M, 3 * E)
-            dgrad(dao_p, w["wo_t"], None, M, E, E, out_planes=do_p)
-            ops.self_attn_bwd(S["qkv_p"], do_p, seg, dqkv_p, S["lse"], dsum_ws, batch=B, heads=H, L=L, head_dim=hd, scale=scale,
-                              drop=drop(s0), o=S["o_p"])
+            if "qkv_b" in S:                # the single-plane attention (bf16_attention): do and dQ | dK | dV as ONE plane each
+                wgrad(ws, dao_p, S["o_b"], G[att.final_linear.weight], G[att.final_linear.bias], M, E, E)
+                do_b, dqkv_p = ws.plane("bwd:do_b", M, E), ws.plane("bwd:dqkv_b", M, 3 * E)
+                dgrad(dao_p, w["wo_t"], None, M, E, E, out_plane=do_b)
+                ops.self_attn_bwd_bf16(S["qkv_b"], do_b, seg, dqkv_p, ws.vec("attn_lse", B * H * L), dsum_ws, batch=B, heads=H, L=L,
+                                       head_dim=hd, scale=scale, drop=drop(s0))
+            else:
+                wgrad(ws, dao_p, S["o_p"], G[att.final_linear.weight], G[att.final_linear.bias], M, E, E)
+                do_p, dqkv_p = pl("do_p", M, E), pl("dqkv_p", M, 3 * E)
+                dgrad(dao_p, w["wo_t"], None, M, E, E, out_planes=do_p)
+                ops.self_attn_bwd(S["qkv_p"], do_p, seg, dqkv_p, S["lse"], dsum_ws, batch=B, heads=H, L=L, head_dim=hd, scale=scale,
+                                  drop=drop(s0), o=S["o_p"])
             wgrad(ws, dqkv_p, S["x_b"], qkv_blocks[i][0], qkv_blocks[i][1], M, E, 3 * E)     # = the three gradients
             dprev = torch.empty(M, E, device=dev) if i == 0 else mat("dh%d" % flip, M, E)
             flip ^= 1

@@ -1,7 +1,7 @@
 """Dual-encoder forward micro-benchmark (ViT-B/16 + RoBERTa-base, random weights, batch 32 of the repo's default shapes).
 Prints ms per forward, algorithmic TFLOP/s (2MNK of the GEMMs + 4 L^2 d of attention) and a per-kernel-class breakdown
 from HIP events.  python tools/encoder_bench.py [--batch 32] [--iters 10] [--passes 3]
---train [--precision mxfp8_train | bf16_train] [--recompute]: forward + backward per step, and the step's peak device memory."""
+--train [--precision mxfp8_train | bf16_train [--bf16-attention]] [--recompute]: forward + backward per step, and the step's peak device memory."""
 import argparse
 import os
 import sys
@@ -95,7 +95,12 @@ def main():
     ap.add_argument("--recompute", action="store_true",
                     help="--train: keep each layer's input only and re-run a layer's forward in front of its backward "
                          "(TransformerEncoder.recompute); the peak-memory figure shows what that buys, the step time what it costs")
+    ap.add_argument("--bf16-attention", action="store_true",
+                    help="--train --precision bf16_train: the attention core on ONE bf16 plane per operand too "
+                         "(TransformerEncoder.bf16_attention)")
     a = ap.parse_args()
+    if a.bf16_attention and not (a.train and a.precision == "bf16_train"):
+        ap.error("--bf16-attention is a switch of --train --precision bf16_train")
     if a.recompute and not a.train:
         ap.error("--recompute is a switch of the training schedule: give --train")
     if a.precision == "bf16_train" and not a.train:
@@ -120,6 +125,7 @@ def main():
         enc = enc.train() if a.train else enc.eval()
         enc.fp8_train = a.train and a.precision == "mxfp8_train"
         enc.bf16_train = a.train and a.precision == "bf16_train"
+        enc.bf16_attention = a.bf16_attention
         enc.recompute = a.recompute
         B = (a.batch * 16 if name.startswith("vit") else a.batch * 2) if a.ppo_shapes else a.batch
         emb = torch.randn(B, L, 768, device=dev, requires_grad=a.train)
