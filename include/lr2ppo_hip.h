@@ -170,11 +170,13 @@ int lr2_layernorm_bwd(const void* dy, int group, uint64_t group_stride, const vo
                       const void* rstd, const void* resid_grad, void* dx, void* dxm_hi, uint64_t dxm_lo_off, float drop_p,
                       uint64_t drop_seed, uint32_t drop_site, const void* drop_seed_dev, void* partials, int nblocks, int rows, int D,
                       int mode, float eps, void* stream);
-/* out[c] = sum_b partials[b*ld + c] for c < cols (deterministic second stage of column reductions). */
+/* out[c] (+)= sum_b partials[b*ld + c] for c < cols (deterministic second stage of column reductions; accumulate != 0 adds to out).
+ * ld >= cols, else LR2_ERR_SHAPE. */
 int lr2_colsum_partials_finish(const void* partials, int nblocks, int cols, int ld, void* out, int accumulate,
                                void* stream);
 /* Column sums of a [rows, cols] matrix (fp32, or bf16 planes with the lo plane lo_off elements after the hi plane; is_planes == 2
  * (ABI 22): ONE bf16 plane, lo_off unused) -> fp32 [cols] (bias gradients); partials: workspace [nblocks][cols].
+ * cols % 4 == 0, ld % 4 == 0, ld >= cols, else LR2_ERR_SHAPE.
  * replaces: autograd of the nn.Linear bias add. */
 int lr2_colsum(const void* x, int is_planes, uint64_t lo_off, int rows, int cols, int ld, void* partials, int nblocks,
                void* out, void* stream);
@@ -246,7 +248,8 @@ int lr2_self_attn_plan(int batch, int heads, int L, int ld, int ld_do, int* fwd_
  * replaces: self.head = nn.Linear(768, 1) and the last-position select (finetune/ppo.py:228-232,293-295). */
 int lr2_head_fwd(const void* x, const void* w, const void* b, void* y, int rows, int D, int row_step, int row_off,
                  void* stream);
-/* dx[total_rows, D] = 0 except dx[row(r)] = dy[r]*w;  dw = sum_r dy[r]*x[row(r)];  db = sum_r dy[r]. */
+/* dx[total_rows, D] = 0 except dx[row(r)] = dy[r]*w for r < rows (total_rows may exceed rows*row_step: the rows beyond are 0);
+ * dw = sum_r dy[r]*x[row(r)];  db = sum_r dy[r].  dx may be NULL; dw and db are written together or not at all. */
 int lr2_head_bwd(const void* x, const void* w, const void* dy, void* dx, void* dw, void* db, int rows, int D,
                  int row_step, int row_off, int total_rows, void* stream);
 

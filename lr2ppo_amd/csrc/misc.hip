@@ -221,14 +221,14 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const float* __restrict__
 }
 
 __global__ __launch_bounds__(256) void head_bwd_dx_kernel(const float* __restrict__ w, const float* __restrict__ dy,
-                                                          float* __restrict__ dx, int D, int row_step, int row_off,
+                                                          float* __restrict__ dx, int rows, int D, int row_step, int row_off,
                                                           int total_rows) {
   const int d4 = D / 4;
   const size_t total = (size_t)total_rows * d4;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
     const int row = (int)(i / d4), c = (int)(i % d4) * 4;
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (row % row_step == row_off) {
+    if (row % row_step == row_off && row / row_step < rows) {      // total_rows may exceed rows * row_step: dy has `rows` entries
       const float g = dy[row / row_step];
       const float4 ww = *reinterpret_cast<const float4*>(w + c);
       v = make_float4(g * ww.x, g * ww.y, g * ww.z, g * ww.w);
@@ -326,14 +326,37 @@ __global__ __launch_bounds__(1024) void ppo_loss_kernel(const float* __restrict_
         zs += p[t];
         zo += qo[t];
       }
+    float pmin = 1.f;
 #pragma unroll
     for (int t = 0; t < PPO_MAX_T; ++t)
       if (t < T) {
         p[t] /= zs;
         qo[t] /= zo;
-        if (kl_w > 0.f) kl += qo[t] * (clamped_log(qo[t]) - clamped_log(p[t]));
+        pmin = fminf(pmin, fminf(p[t], qo[t]));
         if (ent_w > 0.f) ent -= p[t] * clamped_log(p[t]);
       }
+    if (kl_w > 0.f) {
+      if (pmin >= 1e-20f) {
+        // No clamp is active, so log q_t - log p_t = d_t - log(zo' / zs) with d_t the SHIFTED logit difference and
+        // zo' / zs = sum_t p_t e^(d_t) = 1 + sum_t p_t expm1(d_t): KL = sum_t q_t d_t - log1p(sum_t p_t expm1(d_t)).  The two logs
+        // of the textbook form are O(1) each, rounded to an ulp of that (6e-8 .. 2.4e-7), and KL is their O(1e-3) difference; here
+        // every term is of KL's own size.  |d_t| <= 2 x 46 (both probabilities >= 1e-20) and the sum stays in [1/T - 1, T - 1].
+        const float dm = mo - mx;
+        float a = 0.f, e = 0.f;
+#pragma unroll
+        for (int t = 0; t < PPO_MAX_T; ++t)
+          if (t < T) {
+            const float d = (old_scores[(size_t)i * T + t] - s[t]) - dm;
+            a += qo[t] * d;
+            e += p[t] * expm1f(d);
+          }
+        kl = a - log1pf(e);
+      } else {
+#pragma unroll
+        for (int t = 0; t < PPO_MAX_T; ++t)
+          if (t < T) kl += qo[t] * (clamped_log(qo[t]) - clamped_log(p[t]));
+      }
+    }
     r = rewards[i] - kl * kl_w;
     adv = r - old_value[i];
     const bool keep = adv >= adv_eps;
@@ -942,7 +965,7 @@ extern "C" int lr2_head_bwd(const void* x, const void* w, const void* dy, void* 
   hipStream_t s = (hipStream_t)stream;
   if (dx) {
     LR2_LAUNCH(head_bwd_dx_kernel, dim3(grid_for((size_t)total_rows * D / 4)), dim3(256), 0, s, (const float*)w,
-                       (const float*)dy, (float*)dx, D, row_step, row_off, total_rows);
+                       (const float*)dy, (float*)dx, rows, D, row_step, row_off, total_rows);
     if (lr2_launch_status(__func__)) return LR2_ERR_LAUNCH;
   }
   if (dw && db) {

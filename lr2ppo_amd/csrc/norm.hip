@@ -318,6 +318,7 @@ extern "C" int lr2_layernorm_bwd(const void* dy, int group, uint64_t group_strid
 extern "C" int lr2_colsum_partials_finish(const void* partials, int nblocks, int cols, int ld, void* out, int accumulate,
                                           void* stream) {
   if (!partials || !out || nblocks <= 0 || cols <= 0) return LR2_ERR_ARG;
+  if (ld < cols) return LR2_ERR_SHAPE;          // a row pitch below the row length (or negative: reads in front of the buffer)
   LR2_LAUNCH(partials_finish_kernel, dim3((cols + 63) / 64), dim3(256), 0, (hipStream_t)stream,
                      (const float*)partials, nblocks, cols, ld, (float*)out, accumulate);
   return lr2_launch_status(__func__);
@@ -326,7 +327,7 @@ extern "C" int lr2_colsum_partials_finish(const void* partials, int nblocks, int
 extern "C" int lr2_colsum(const void* x, int is_planes, uint64_t lo_off, int rows, int cols, int ld, void* partials,
                           int nblocks, void* out, void* stream) {
   if (!x || !partials || !out || rows <= 0 || cols <= 0 || nblocks <= 0) return LR2_ERR_ARG;
-  if (cols % 4 != 0 || ld % 4 != 0) return LR2_ERR_SHAPE;
+  if (cols % 4 != 0 || ld % 4 != 0 || ld < cols) return LR2_ERR_SHAPE;
   if (nblocks > rows) nblocks = rows;
   dim3 grid((cols + 1023) / 1024, nblocks);
   if (is_planes == 2)

@@ -355,8 +355,10 @@ def test_ppo_loss_and_gradients(ops, dev, B, T, seed):
     state = torch.stack([torch.randperm(T, generator=g) for _ in range(B)])
     nxt = torch.cat([torch.arange(2).unsqueeze(0).repeat(B, 1), state], dim=1)
     kl_w, ent_w, clip = 0.001, 0.001, 0.5
-    st, vt = scores.clone().requires_grad_(True), value.clone().requires_grad_(True)
-    loss, vloss, ex = O.ppo_update_math(st, vt, old, rewards, old_value, nxt, kl_w, ent_w, clip)
+    # fp64 reference: an fp32 evaluation of KL = sum q (log q - log p) is itself off by 1.5e-7 (two O(1) logs, subtracted), more than
+    # the 1e-7 asked of the kernel below
+    st, vt = scores.double().requires_grad_(True), value.double().requires_grad_(True)
+    loss, vloss, ex = O.ppo_update_math(st, vt, old.double(), rewards.double(), old_value.double(), nxt, kl_w, ent_w, clip)
     loss.backward()
     vloss.backward()
     scal, per = torch.empty(4, device=dev), torch.empty(4, B, device=dev)
