@@ -24,7 +24,7 @@ extern "C" {
 #define LR2_ERR_SHAPE (-2)  /* shape not supported by the kernel's tiling */
 #define LR2_ERR_LAUNCH (-3) /* HIP launch failure */
 
-#define LR2_ABI_VERSION 23
+#define LR2_ABI_VERSION 24
 int lr2_abi_version(void);
 /* Fills name[0..len) with the HIP device name and returns the CU count (or <0). */
 int lr2_device_info(char* name, int len);
@@ -484,6 +484,38 @@ int lr2_self_attn_bwd_bf16(const void* q, const void* k, const void* v, int ld, 
  * lr2_self_attn_bwd_bf16 calls since the library was loaded.
  * replaces: nothing (a test hook: which attention a schedule ran; multi_headed_attn.py:61-74 has no counterpart). */
 int lr2_self_attn_bf16_train_launch_counts(uint64_t counts[2]);
+
+/* ABI 24.  The same attention for sequences longer than one LDS-resident head (FeatureExtractor(precision="bf16_train",
+ * bf16_attention=True, bf16_attention_long=True); csrc/selfattn_b1_blocked.hip): the argument lists, the layout, the
+ * arithmetic contract, the key mask, the dropout mask stream and the rounding sites of lr2_self_attn_fwd_bf16_train /
+ * lr2_self_attn_bwd_bf16, with the keys (forward, dQ) or the queries (dK / dV) walked in blocks through LDS; head_dim 64, any L >= 1
+ * (so 1 <= L <= 288 can be run in both forms), one workgroup of 8 waves per (sequence, head, chunk of query or key sub-tiles).
+ *   lr2_self_attn_fwd_bf16_train_blocked: K and V of one key block in LDS (lr2_self_attn_fwd's blocked rule: ceil(L / 224) equal rounded
+ *       blocks of 160, 192 or 224 keys); per 16-query sub-tile a running maximum m, the sum l of the unrounded, un-dropped
+ *       p~ = exp2(s - m) and the un-normalised accumulator, both rescaled by exp2(m - m') in fp32 when m grows; p~ * mask is rounded to
+ *       bf16 as the A operand of P V; o_bf16 = accumulator / l as one bf16 plane; lse (optional) = m + log l in natural-log units.
+ *   lr2_self_attn_bwd_bf16_blocked: two launches.  dQ, two sweeps over key blocks of 256: sweep 1 keeps m, l and a = sum exp(s - m) dP
+ *       and writes lse_ws = m + log l and dsum_ws = D = a / l; sweep 2 forms dS = P (dP - D) scale, rounds it to bf16, dQ += dS K.
+ *       dK / dV: a wave holds 16 keys' K and V fragments and accumulators while Q, dO, lse and D pass through LDS in blocks of 256
+ *       queries; Pd = P o M and dS are rounded to bf16.  Outputs: round to nearest even of the fp32 accumulators.  No atomics.
+ * Errors as the two calls above with L >= 1 as the only length rule; nothing is launched by a rejected call.
+ * replaces: tencentpretrain/layers/multi_headed_attn.py:61-74 (scores, mask, softmax, dropout, context) and its autograd, in that mode
+ * at the sequence lengths the one-block kernels do not serve. */
+int lr2_self_attn_fwd_bf16_train_blocked(const void* q, const void* k, const void* v, int ld, const int64_t* seg, void* o_bf16, int ld_o,
+                                         void* lse, float drop_p, uint64_t drop_seed, uint32_t drop_site, int batch, int heads, int L,
+                                         int head_dim, float scale, void* stream);
+int lr2_self_attn_bwd_bf16_blocked(const void* q, const void* k, const void* v, int ld, const void* d_o, int ld_do, const int64_t* seg,
+                                   void* dq, void* dk, void* dv, int ld_d, void* lse_ws, void* dsum_ws, float drop_p, uint64_t drop_seed,
+                                   uint32_t drop_site, int batch, int heads, int L, int head_dim, float scale, void* stream);
+/* Host only: the block lengths the two calls above use at this L (each launcher calls the helper this does): *fwd_key_block keys per
+ * block of the forward, *dq_key_block keys per block of the dQ launch, *dkv_query_block queries per block of the dK / dV launch; NULL
+ * pointers are skipped.  LR2_ERR_ARG for L < 1.
+ * replaces: nothing (tests lay their masks on these blocks; multi_headed_attn.py:61-74 has no counterpart). */
+int lr2_self_attn_bf16_blocked_plan(int L, int* fwd_key_block, int* dq_key_block, int* dkv_query_block);
+/* Diagnostic: counts[0] = accepted lr2_self_attn_fwd_bf16_train_blocked calls, counts[1] = accepted lr2_self_attn_bwd_bf16_blocked calls
+ * since the library was loaded.
+ * replaces: nothing (a test hook, as lr2_self_attn_bf16_train_launch_counts). */
+int lr2_self_attn_bf16_blocked_launch_counts(uint64_t counts[2]);
 
 /* ABI 20.  MX-FP8 encoder training (FeatureExtractor(precision="mxfp8_train")): the backward's operands, blocked along the axis its
  * products reduce over, and a K-sliced weight-gradient product.

@@ -1135,7 +1135,8 @@ def self_attn_fwd_bf16_train(qkv: torch.Tensor, seg, out_plane: torch.Tensor, *,
                              lse: Optional[torch.Tensor] = None, drop: Optional[Drop] = None):
     """Encoder self-attention of the bf16_train mode, forward (lr2_self_attn_fwd_bf16_train).  qkv: ONE bf16 plane [batch * L, 3E] =
     [Q | K | V] (what gemm_bf16_train(out_plane=...) writes); out_plane: the context as ONE bf16 plane [batch * L, E]; lse: optional
-    fp32 [batch * heads * L]; drop: dropout on the probabilities (self_attn_fwd's mask stream).  head_dim 64, L <= 288."""
+    fp32 [batch * heads * L]; drop: dropout on the probabilities (self_attn_fwd's mask stream).  head_dim 64; L <= 288 runs the
+    one-block kernels, a longer sequence the key-blocked ones (lr2_self_attn_fwd_bf16_train_blocked: the same arithmetic contract)."""
     E = _attn_plane_args("self_attn_fwd_bf16_train", seg, batch, heads, L, head_dim, (("qkv", qkv, 3 * heads * head_dim),
                                                                                      ("out_plane", out_plane, heads * head_dim)))
     _chk_f32(lse)
@@ -1144,17 +1145,18 @@ def self_attn_fwd_bf16_train(qkv: torch.Tensor, seg, out_plane: torch.Tensor, *,
     q, k, v = _qkv_ptrs(qkv, E)
     p, seed, site = (drop.p, drop.seed, drop.site) if drop is not None else (0.0, 0, 0)
     with _Timed(f"selfattn_b1t_B{batch}_H{heads}_L{L}", 4.0 * batch * heads * L * L * head_dim, 8.0 * batch * L * E):
-        _nat.check(_nat.lib().lr2_self_attn_fwd_bf16_train(q, k, v, 3 * E, seg.data_ptr(), out_plane.data_ptr(), E, _ptr(lse), p, seed,
-                                                           site, batch, heads, L, head_dim, scale, _stream()),
-                   "lr2_self_attn_fwd_bf16_train")
+        name = "lr2_self_attn_fwd_bf16_train" if L <= 288 else "lr2_self_attn_fwd_bf16_train_blocked"
+        _nat.check(getattr(_nat.lib(), name)(q, k, v, 3 * E, seg.data_ptr(), out_plane.data_ptr(), E, _ptr(lse), p, seed, site, batch,
+                                             heads, L, head_dim, scale, _stream()), name)
     return out_plane
 
 
 def self_attn_bwd_bf16(qkv: torch.Tensor, do: torch.Tensor, seg, dqkv: torch.Tensor, lse_ws, dsum_ws, *, batch, heads, L, head_dim,
                        scale, drop: Optional[Drop] = None):
     """dQKV (ONE bf16 plane [batch * L, 3E]) from QKV [batch * L, 3E] and dO [batch * L, E] (ONE bf16 plane each) by the recomputing
-    single-plane backward (lr2_self_attn_bwd_bf16); lse_ws / dsum_ws: fp32 [batch * heads * L] scratch.  `drop` as in the forward
-    replays its mask; the forward's output and log-sum-exp are not needed."""
+    single-plane backward (lr2_self_attn_bwd_bf16; L > 288: lr2_self_attn_bwd_bf16_blocked); lse_ws / dsum_ws: fp32
+    [batch * heads * L] scratch at any L.  `drop` as in the forward replays its mask; the forward's output and log-sum-exp are not
+    needed."""
     E = _attn_plane_args("self_attn_bwd_bf16", seg, batch, heads, L, head_dim, (("qkv", qkv, 3 * heads * head_dim),
                                                                                ("do", do, heads * head_dim),
                                                                                ("dqkv", dqkv, 3 * heads * head_dim)))
@@ -1165,9 +1167,9 @@ def self_attn_bwd_bf16(qkv: torch.Tensor, do: torch.Tensor, seg, dqkv: torch.Ten
     dq, dk, dv = _qkv_ptrs(dqkv, E)
     p, seed, site = (drop.p, drop.seed, drop.site) if drop is not None else (0.0, 0, 0)
     with _Timed(f"selfattnbwd_b1t_B{batch}_H{heads}_L{L}", 14.0 * batch * heads * L * L * head_dim, 16.0 * batch * L * E):
-        _nat.check(_nat.lib().lr2_self_attn_bwd_bf16(q, k, v, 3 * E, do.data_ptr(), E, seg.data_ptr(), dq, dk, dv, 3 * E,
-                                                     lse_ws.data_ptr(), dsum_ws.data_ptr(), p, seed, site, batch, heads, L, head_dim,
-                                                     scale, _stream()), "lr2_self_attn_bwd_bf16")
+        name = "lr2_self_attn_bwd_bf16" if L <= 288 else "lr2_self_attn_bwd_bf16_blocked"
+        _nat.check(getattr(_nat.lib(), name)(q, k, v, 3 * E, do.data_ptr(), E, seg.data_ptr(), dq, dk, dv, 3 * E, lse_ws.data_ptr(),
+                                             dsum_ws.data_ptr(), p, seed, site, batch, heads, L, head_dim, scale, _stream()), name)
     return dqkv
 
 
@@ -1175,6 +1177,21 @@ def self_attn_bf16_train_launch_counts():
     """(forward, backward) calls of the single-plane training attention since the library was loaded."""
     c = (C.c_uint64 * 2)()
     _nat.check(_nat.lib().lr2_self_attn_bf16_train_launch_counts(c), "lr2_self_attn_bf16_train_launch_counts")
+    return int(c[0]), int(c[1])
+
+
+def self_attn_bf16_blocked_plan(L: int):
+    """(forward key block, dQ key block, dK / dV query block): the block lengths the blocked single-plane training attention uses at
+    this L (lr2_self_attn_bf16_blocked_plan; host only)."""
+    f, q, kv = C.c_int(), C.c_int(), C.c_int()
+    _nat.check(_nat.lib().lr2_self_attn_bf16_blocked_plan(L, C.byref(f), C.byref(q), C.byref(kv)), "lr2_self_attn_bf16_blocked_plan")
+    return f.value, q.value, kv.value
+
+
+def self_attn_bf16_blocked_launch_counts():
+    """(forward, backward) calls of the BLOCKED single-plane training attention since the library was loaded."""
+    c = (C.c_uint64 * 2)()
+    _nat.check(_nat.lib().lr2_self_attn_bf16_blocked_launch_counts(c), "lr2_self_attn_bf16_blocked_launch_counts")
     return int(c[0]), int(c[1])
 
 

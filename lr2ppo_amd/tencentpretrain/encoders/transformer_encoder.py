@@ -174,6 +174,9 @@ class TransformerEncoder(nn.Module):
     # backward (ops.self_attn_fwd_bf16_train / ops.self_attn_bwd_bf16; FeatureExtractor(..., bf16_attention=True)); every
     # other layer shape keeps the 3-pass kernels
     bf16_attention = False
+    # True (with bf16_attention): a layer with head_dim 64 and L > 288 takes the single-plane attention too, on the key- / query-blocked
+    # kernels of csrc/selfattn_b1_blocked.hip (the same ops calls; FeatureExtractor(..., bf16_attention_long=True))
+    bf16_attention_long = False
 
     def __init__(self, args):
         super().__init__()
@@ -1009,7 +1012,8 @@ class TransformerEncoder(nn.Module):
     # _forward_train / _backward_train in the same order, with the same dropout sites, `saved` / G contract and gradient layout, but every
     # projection -- forward, input gradient, weight gradient -- ONE bf16 pass with fp32 accumulation (ops.gemm_bf16_train:
     # csrc/gemm256_b1.hip, csrc/gemm256_tn_b1.hip, the 128- / 64-row family at passes = 1).  The attention (3-pass planes kernels on hi / lo
-    # qkv_p, o_p, do_p, dqkv_p; with bf16_attention and head_dim 64, L <= 288: the single-plane kernels of csrc/selfattn_b1_train.hip
+    # qkv_p, o_p, do_p, dqkv_p; with bf16_attention and head_dim 64, L <= 288 -- any L with bf16_attention_long: the single-plane kernels
+    # of csrc/selfattn_b1_train.hip / selfattn_b1_blocked.hip
     # on ONE plane qkv_b, o_b, do_b, dqkv_b each), every LayerNorm, the fp32 residual stream and the fp32 master weights stay as they
     # are.  An activation that only feeds products (LayerNorm outputs, GELU(z)) is kept as ONE plane; a product reads the hi plane
     # (= bf16(x)) of a tensor that exists as hi / lo planes for another reader.
@@ -1035,8 +1039,9 @@ class TransformerEncoder(nn.Module):
         return self._bf16t_w
 
     def _b1_attention(self, hd, L):
-        """Does a bf16_train layer of this shape take the single-plane attention (csrc/selfattn_b1_train.hip)?"""
-        return bool(self.bf16_train and self.bf16_attention and hd == 64 and L <= 288)
+        """Does a bf16_train layer of this shape take the single-plane attention (csrc/selfattn_b1_train.hip; L > 288 with
+        bf16_attention_long: csrc/selfattn_b1_blocked.hip)?"""
+        return bool(self.bf16_train and self.bf16_attention and hd == 64 and (L <= 288 or self.bf16_attention_long))
 
     def _layer_fwd_train_bf16(self, i, w, h, h_b, A, seg, dims, drop):
         """Layer i of the bf16 training schedule.  h: the layer's input [M, E] (fp32); h_b: its bf16 plane (post-LN; None for pre-LN);

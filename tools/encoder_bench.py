@@ -1,7 +1,8 @@
 """Dual-encoder forward micro-benchmark (ViT-B/16 + RoBERTa-base, random weights, batch 32 of the repo's default shapes).
 Prints ms per forward, algorithmic TFLOP/s (2MNK of the GEMMs + 4 L^2 d of attention) and a per-kernel-class breakdown
 from HIP events.  python tools/encoder_bench.py [--batch 32] [--iters 10] [--passes 3]
---train [--precision mxfp8_train | bf16_train [--bf16-attention]] [--recompute]: forward + backward per step, and the step's peak device memory."""
+--train [--precision mxfp8_train | bf16_train [--bf16-attention [--bf16-attention-long]]] [--recompute]: forward + backward per step, and
+the step's peak device memory.  --text-seq L / --only text | image: the text tower at another sequence length / one tower alone."""
 import argparse
 import os
 import sys
@@ -98,7 +99,18 @@ def main():
     ap.add_argument("--bf16-attention", action="store_true",
                     help="--train --precision bf16_train: the attention core on ONE bf16 plane per operand too "
                          "(TransformerEncoder.bf16_attention)")
+    ap.add_argument("--bf16-attention-long", action="store_true",
+                    help="--bf16-attention: sequences longer than 288 on the blocked single-plane kernels too "
+                         "(TransformerEncoder.bf16_attention_long)")
+    ap.add_argument("--text-seq", type=int, default=196, help="sequence length of the text tower (at most 514)")
+    ap.add_argument("--only", choices=("both", "image", "text"), default="both", help="run one tower alone")
     a = ap.parse_args()
+    if a.bf16_attention_long and not a.bf16_attention:
+        ap.error("--bf16-attention-long is a switch of --bf16-attention")
+    if not 1 <= a.text_seq <= ROBERTA["max_seq_length"]:
+        ap.error("--text-seq: 1 .. %d" % ROBERTA["max_seq_length"])
+    if (a.text_seq != 196 or a.only != "both") and a.ppo_shapes and not a.train:
+        ap.error("--text-seq / --only are switches of the per-tower loop: not of --ppo-shapes without --train")
     if a.bf16_attention and not (a.train and a.precision == "bf16_train"):
         ap.error("--bf16-attention is a switch of --train --precision bf16_train")
     if a.recompute and not a.train:
@@ -115,7 +127,9 @@ def main():
         print(measure_forward(a.batch, iters=a.iters, passes=a.passes, dev=dev, precision=prec))
         return
     total_ms, total_fl = 0.0, 0.0
-    for name, cfg, L in (("vit-b/16", VIT, 197), ("roberta-base", ROBERTA, 196)):
+    towers = [t for t in (("vit-b/16", VIT, 197), ("roberta-base", ROBERTA, a.text_seq))
+              if a.only == "both" or t[0].startswith("vit") == (a.only == "image")]
+    for name, cfg, L in towers:
         enc = str2encoder["transformer"](_args(**cfg))
         with torch.no_grad():
             for n, p in enc.named_parameters():
@@ -126,6 +140,7 @@ def main():
         enc.fp8_train = a.train and a.precision == "mxfp8_train"
         enc.bf16_train = a.train and a.precision == "bf16_train"
         enc.bf16_attention = a.bf16_attention
+        enc.bf16_attention_long = a.bf16_attention_long
         enc.recompute = a.recompute
         B = (a.batch * 16 if name.startswith("vit") else a.batch * 2) if a.ppo_shapes else a.batch
         emb = torch.randn(B, L, 768, device=dev, requires_grad=a.train)
