@@ -24,7 +24,7 @@ extern "C" {
 #define LR2_ERR_SHAPE (-2)  /* shape not supported by the kernel's tiling */
 #define LR2_ERR_LAUNCH (-3) /* HIP launch failure */
 
-#define LR2_ABI_VERSION 24
+#define LR2_ABI_VERSION 25
 int lr2_abi_version(void);
 /* Fills name[0..len) with the HIP device name and returns the CU count (or <0). */
 int lr2_device_info(char* name, int len);
@@ -516,6 +516,29 @@ int lr2_self_attn_bf16_blocked_plan(int L, int* fwd_key_block, int* dq_key_block
  * since the library was loaded.
  * replaces: nothing (a test hook, as lr2_self_attn_bf16_train_launch_counts). */
 int lr2_self_attn_bf16_blocked_launch_counts(uint64_t counts[2]);
+
+/* ABI 25.  lr2_self_attn_fwd_bf16 for sequences longer than one LDS-resident head (FeatureExtractor(precision="bf16" | "mxfp8",
+ * attention_long=True); csrc/selfattn_mx_blocked.hip): that call's argument list, layout, key mask and three outputs -- q / k /
+ * v ONE bf16 plane each (row stride ld), the context rows out as fp32 (o_f32 [batch * L, ld_o]) and / or as MX-FP8 (o_q [batch * L, ld_o]
+ * bytes + o_scales [batch * L, ld_o / 32], lr2_quant_mxfp8's rule) and / or as ONE bf16 plane (o_bf16 [batch * L, ld_o], round to nearest
+ * even of the fp32 context); any subset -- with the keys walked in blocks through LDS by lr2_self_attn_fwd_bf16_train_blocked's loop:
+ * lr2_self_attn_bf16_blocked_plan's fwd_key_block keys per block, per 16-query sub-tile a running maximum m, the fp32 sum l of the
+ * unrounded p~ = exp2(s - m) and the un-normalised accumulator, both rescaled by exp2(m - m') when m grows; p~ rounded to bf16 as the A
+ * operand of P V; context = accumulator / l.  No dropout, no lse: o_bf16 is byte-equal to lr2_self_attn_fwd_bf16_train_blocked's at
+ * drop_p = 0.  head_dim 64, any L >= 1 (so 1 <= L <= 288 can be run in both forms), one workgroup of 8 waves per (sequence, head, chunk
+ * of 512 queries).  Inference only.  NOT the parity path: lr2_self_attn_fwd stays the default, and lr2_self_attn_fwd_bf16 is unchanged.
+ * LR2_ERR_ARG: a NULL q / k / v / seg; no output at all; o_q without o_scales or the reverse; q / k / v / o_f32 not 16-byte, o_bf16 not
+ * 8-byte or o_q not 4-byte aligned; batch or heads <= 0.  LR2_ERR_SHAPE: head_dim != 64; L < 1; ld or ld_o below heads * 64 or no
+ * multiple of 8; ld_o % 32 when o_q is given.  Nothing is launched by a rejected call.
+ * replaces: tencentpretrain/layers/multi_headed_attn.py:60-74 in those modes at the sequence lengths lr2_self_attn_fwd_bf16 does not
+ * serve. */
+int lr2_self_attn_fwd_bf16_blocked(const void* q, const void* k, const void* v, int ld, const int64_t* seg, void* o_f32, void* o_q,
+                                   void* o_scales, void* o_bf16, int ld_o, int batch, int heads, int L, int head_dim, float scale,
+                                   void* stream);
+/* Diagnostic: *count = accepted lr2_self_attn_fwd_bf16_blocked calls since the library was loaded (a plain host counter, not
+ * synchronised).  LR2_ERR_ARG for a NULL count.
+ * replaces: nothing (a test hook, as lr2_self_attn_bf16_blocked_launch_counts: which attention a schedule ran). */
+int lr2_self_attn_fwd_bf16_blocked_launch_count(uint64_t* count);
 
 /* ABI 20.  MX-FP8 encoder training (FeatureExtractor(precision="mxfp8_train")): the backward's operands, blocked along the axis its
  * products reduce over, and a K-sliced weight-gradient product.

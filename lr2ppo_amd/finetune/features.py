@@ -165,6 +165,9 @@ class FeatureExtractor(nn.Module):
     (TransformerEncoder.bf16_attention: head_dim 64 and L <= 288, other layer shapes keep the 3-pass kernels).
     bf16_attention_long (with bf16_attention only): sequences longer than 288 take the single-plane attention too, on its blocked kernels
     (TransformerEncoder.bf16_attention_long).
+    attention_long ("bf16" and "mxfp8" only): the two inference modes run sequences longer than 288 (head_dim 64) on ONE bf16 plane per
+    operand too, on the key-blocked kernel of csrc/selfattn_mx_blocked.hip instead of the 3-pass attention
+    (TransformerEncoder.infer_attention_long); sequences up to 288 are unaffected.
     recompute: the training forwards of both towers keep each layer's input only and the backward re-runs a layer's forward right
     before that layer's backward (TransformerEncoder.recompute): the same bits, ~1/12 of the activation memory, one more
     forward per step.  Embeddings, the projection and the heads keep their activations."""
@@ -175,7 +178,7 @@ class FeatureExtractor(nn.Module):
     def __init__(self, vit_args: Optional[argparse.Namespace] = None, text_args: Optional[argparse.Namespace] = None,
                  vocab_size: int = ROBERTA_VOCAB, seq_length: int = 196, feat_dim: Optional[int] = None,
                  precision: str = "split_bf16", recompute: bool = False, bf16_attention: bool = False,
-                 bf16_attention_long: bool = False):
+                 bf16_attention_long: bool = False, attention_long: bool = False):
         super().__init__()
         self.vit_args = vit_args or encoder_args(VIT_CONFIG)
         self.text_args = text_args or encoder_args(TEXT_CONFIG)
@@ -192,8 +195,10 @@ class FeatureExtractor(nn.Module):
             raise ValueError(f"bf16_attention is a switch of precision='bf16_train', not of '{precision}'")
         if bf16_attention_long and not bf16_attention:
             raise ValueError("bf16_attention_long extends bf16_attention to sequences longer than 288: it needs bf16_attention=True")
+        if attention_long and precision not in self.INFERENCE_ONLY:
+            raise ValueError(f"attention_long is a switch of the inference modes {self.INFERENCE_ONLY}, not of '{precision}'")
         self.precision, self.recompute, self.bf16_attention = precision, bool(recompute), bool(bf16_attention)
-        self.bf16_attention_long = bool(bf16_attention_long)
+        self.bf16_attention_long, self.attention_long = bool(bf16_attention_long), bool(attention_long)
         self.image = EncoderStack(self.vit_args, vocab_size)
         self.text = EncoderStack(self.text_args, vocab_size)
         self.visual_projection = (VisualProjection(self.vit_args.hidden_size, self.feat_dim)
@@ -204,6 +209,7 @@ class FeatureExtractor(nn.Module):
         self.image.encoder.recompute = self.text.encoder.recompute = self.recompute
         self.image.encoder.bf16_attention = self.text.encoder.bf16_attention = self.bf16_attention
         self.image.encoder.bf16_attention_long = self.text.encoder.bf16_attention_long = self.bf16_attention_long
+        self.image.encoder.infer_attention_long = self.text.encoder.infer_attention_long = self.attention_long
 
     def saved_activation_bytes(self, frames_shape, ids_shape) -> int:
         """Bytes of encoder activations forward_train keeps until backward_train for frames [B, n_img, ...] and ids [B, T, L]: the
@@ -466,6 +472,9 @@ def raw_input_opts(parser):
     parser.add_argument("--bf16_attention_long", action="store_true",
                         help="with --bf16_attention: sequences longer than 288 on ONE bf16 plane per operand too, on the blocked "
                              "kernels (FeatureExtractor(..., bf16_attention=True, bf16_attention_long=True); head_dim 64)")
+    parser.add_argument("--features_attention_long", action="store_true",
+                        help="with --bf16_features or --fp8_features: sequences longer than 288 on ONE bf16 plane per operand too, on "
+                             "the key-blocked kernel (FeatureExtractor(precision='bf16' | 'mxfp8', attention_long=True); head_dim 64)")
     parser.add_argument("--recompute_activations", action="store_true",
                         help="with --finetune_encoders: keep one layer's activations at a time (each layer's forward runs again "
                              "in front of its backward: same gradients, ~1/12 of the activation memory, one more forward per step)")
@@ -498,6 +507,9 @@ def build_extractor(args, num_tasks: int = 1, trainable: bool = False) -> Featur
     bf16_attention_long = bool(getattr(args, "bf16_attention_long", False))
     if bf16_attention_long and not bf16_attention:
         raise ValueError("--bf16_attention_long is a switch of the single-plane bf16 attention: it needs --bf16_attention")
+    attention_long = bool(getattr(args, "features_attention_long", False))
+    if attention_long and not (bf16 or fp8):
+        raise ValueError("--features_attention_long is a switch of the inference modes: it needs --bf16_features or --fp8_features")
     recompute = bool(getattr(args, "recompute_activations", False))
     if recompute and not trainable:
         raise ValueError("--recompute_activations is a training-memory switch: it needs --finetune_encoders")
@@ -505,7 +517,8 @@ def build_extractor(args, num_tasks: int = 1, trainable: bool = False) -> Featur
                                                                ("bf16_train" if bf16_train else "split_bf16")))
     fx = FeatureExtractor(encoder_args(IMAGE_TOWERS.get(tower, tower), **over), encoder_args(TEXT_CONFIG, **over),
                           seq_length=args.seq_length, feat_dim=args.visual_feat_dim, precision=precision,
-                          recompute=recompute, bf16_attention=bf16_attention, bf16_attention_long=bf16_attention_long)
+                          recompute=recompute, bf16_attention=bf16_attention, bf16_attention_long=bf16_attention_long,
+                          attention_long=attention_long)
     text_path, vit_path = getattr(args, "pretrained_model_path", None), getattr(args, "vit_pretrained_model_path", None)
     if text_path or vit_path:
         if not (text_path and vit_path):

@@ -1112,6 +1112,38 @@ def self_attn_fwd_bf16(qkv: torch.Tensor, seg, *, batch, heads, L, head_dim, sca
     return out if out is not None else (out_mx if out_mx is not None else out_plane)
 
 
+def self_attn_fwd_bf16_blocked(qkv: torch.Tensor, seg, *, batch, heads, L, head_dim, scale, out: Optional[torch.Tensor] = None,
+                               out_mx: Optional[Mx8] = None, out_plane: Optional[torch.Tensor] = None):
+    """self_attn_fwd_bf16 with the keys walked in blocks through LDS (lr2_self_attn_fwd_bf16_blocked, csrc/selfattn_mx_blocked.hip): the
+    same arguments, checks and outputs at any L >= 1 -- what the bf16 and MX-FP8 inference schedules run above 288 tokens with
+    TransformerEncoder.infer_attention_long.  The plane is byte-equal to self_attn_fwd_bf16_train's at the same L without dropout."""
+    E = heads * head_dim
+    if qkv.element_size() != 2 or not qkv.is_cuda or qkv.numel() < batch * L * 3 * E:
+        raise TypeError("self_attn_fwd_bf16_blocked: qkv is a 2-byte HIP tensor [batch * L, 3 * heads * head_dim]")
+    if seg.dtype != torch.int64:
+        raise TypeError("seg must be int64")
+    _chk_f32(out)
+    if out is None and out_mx is None and out_plane is None:
+        raise ValueError("self_attn_fwd_bf16_blocked: out and / or out_mx and / or out_plane")
+    ob = _plane_ptr(out_plane, batch * L * E, "self_attn_fwd_bf16_blocked: out_plane") if out_plane is not None else None
+    if out_mx is not None and (out_mx.rows != batch * L or out_mx.cols != E):
+        raise ValueError("self_attn_fwd_bf16_blocked: out_mx must be [batch * L, heads * head_dim]")
+    base = qkv.data_ptr()
+    with _Timed(f"selfattn_bf16l_B{batch}_H{heads}_L{L}", 4.0 * batch * heads * L * L * head_dim, 7.0 * batch * L * E):
+        _nat.check(_nat.lib().lr2_self_attn_fwd_bf16_blocked(base, base + 2 * E, base + 4 * E, 3 * E, seg.data_ptr(), _ptr(out),
+                                                             out_mx.q.data_ptr() if out_mx is not None else None,
+                                                             out_mx.s.data_ptr() if out_mx is not None else None, ob, E, batch, heads,
+                                                             L, head_dim, scale, _stream()), "lr2_self_attn_fwd_bf16_blocked")
+    return out if out is not None else (out_mx if out_mx is not None else out_plane)
+
+
+def self_attn_fwd_bf16_blocked_launch_count() -> int:
+    """Accepted self_attn_fwd_bf16_blocked calls since the library was loaded (a test hook: which attention a schedule ran)."""
+    c = C.c_uint64()
+    _nat.check(_nat.lib().lr2_self_attn_fwd_bf16_blocked_launch_count(C.byref(c)), "lr2_self_attn_fwd_bf16_blocked_launch_count")
+    return int(c.value)
+
+
 def self_attn_bf16_plan(batch: int, heads: int, L: int, ld: Optional[int] = None) -> bool:
     """True when self_attn_fwd_bf16 runs a call of this shape as persistent workgroups (lr2_self_attn_fwd_bf16_plan)."""
     f = C.c_int()

@@ -177,6 +177,10 @@ class TransformerEncoder(nn.Module):
     # True (with bf16_attention): a layer with head_dim 64 and L > 288 takes the single-plane attention too, on the key- / query-blocked
     # kernels of csrc/selfattn_b1_blocked.hip (the same ops calls; FeatureExtractor(..., bf16_attention_long=True))
     bf16_attention_long = False
+    # True: the two inference-only schedules (forward_bf16, forward_fp8) run a layer with head_dim 64 and L > 288 on ONE bf16 plane per
+    # operand too, on the key-blocked kernel of csrc/selfattn_mx_blocked.hip (ops.self_attn_fwd_bf16_blocked;
+    # FeatureExtractor(precision="bf16" | "mxfp8", attention_long=True)); off: the 3-pass attention kernels above 288
+    infer_attention_long = False
 
     def __init__(self, args):
         super().__init__()
@@ -307,7 +311,9 @@ class TransformerEncoder(nn.Module):
     @torch.no_grad()
     def forward_fp8(self, emb, seg, first_only: bool = False):
         """forward(emb, seg) with the four projections of every layer as MX-FP8 products (csrc/fp8.hip); LayerNorm, attention and the
-        residual stream stay fp32 / split-bf16.  An element keeps 3 mantissa bits: expect the output a few per cent away from
+        residual stream stay fp32 / split-bf16 (head width 64, L <= 288: single-plane bf16 attention, the context straight to MX-FP8;
+        L > 288: the 3-pass kernels and a quantise pass, or with infer_attention_long ops.self_attn_fwd_bf16_blocked writing MX-FP8;
+        LR2_FP8_ATTN=0 forces the 3-pass kernels at every L).  An element keeps 3 mantissa bits: expect the output a few per cent away from
         forward()'s -- the throughput mode of BASELINE.json configs[4] (FeatureExtractor(precision="mxfp8")), never the parity path.
         first_only: -> hidden[:, 0, :] ([batch, hidden]); the last layer then computes keys / values for every row (MX-FP8) and
         everything behind the scores for row 0 only (forward_first_token's schedule, B rows: split-bf16)."""
@@ -327,7 +333,9 @@ class TransformerEncoder(nn.Module):
         h, h2, xn = ws.mat("h", M, E), ws.mat("h2", M, E), ws.mat("fp8_xn", M, E)
         o32 = ws.mat("fp8_o", M, E)
         qkv_p = ws.planes("qkv_p", M, 3 * E)
-        fast_attn = hd == 64 and L <= 288 and os.environ.get("LR2_FP8_ATTN", "1") != "0"     # (longer sequences: the 3-pass kernels)
+        # (longer sequences: the 3-pass kernels, or with infer_attention_long the key-blocked single-plane kernel)
+        fast_attn = hd == 64 and (L <= 288 or self.infer_attention_long) and os.environ.get("LR2_FP8_ATTN", "1") != "0"
+        attn_b1 = ops.self_attn_fwd_bf16 if L <= 288 else ops.self_attn_fwd_bf16_blocked
         qkv_b = qkv_p.buf[:M * 3 * E]
         if getattr(self, "_fp8_act", None) is None or self._fp8_act[0].rows != M:
             self._fp8_act = (ops.Mx8.empty(M, E, dev), ops.Mx8.empty(M, F, dev))
@@ -347,7 +355,7 @@ class TransformerEncoder(nn.Module):
             if fast_attn:
                 # Q | K | V as ONE bf16 plane, single-pass attention, context straight to MX-FP8 (csrc/selfattn_mx.hip)
                 ops.gemm_mxfp8(x_q, w["wqkv"], None, bias=w["bqkv"], out_bf16=qkv_b)
-                ops.self_attn_fwd_bf16(qkv_b, seg, batch=B, heads=H, L=L, head_dim=hd, scale=scale, out_mx=x_q)
+                attn_b1(qkv_b, seg, batch=B, heads=H, L=L, head_dim=hd, scale=scale, out_mx=x_q)
             else:
                 ops.gemm_mxfp8(x_q, w["wqkv"], None, bias=w["bqkv"], out_planes=qkv_p)     # the 3-pass attention kernels take bf16 hi / lo planes
                 ops.self_attn_fwd(qkv_p, seg, o32, batch=B, heads=H, L=L, head_dim=hd, scale=scale)
@@ -380,7 +388,8 @@ class TransformerEncoder(nn.Module):
         GELU(z) are written as a single plane each by the kernel that produces them; the residual stream stays fp32.  The weights are
         the hi planes of _weight_planes (hi == bf16(W)): no copy, no cache of their own.  A third of the parity path's matrix work
         and half its activation traffic; features 4-7e-3 (relative) from forward()'s -- FeatureExtractor(precision="bf16").
-        L > 288: the 3-pass attention kernels (the QKV product then writes hi / lo planes, the context goes through split_planes).
+        L > 288: the 3-pass attention kernels (the QKV product then writes hi / lo planes, the context goes through split_planes);
+        with infer_attention_long the key-blocked single-plane kernel (ops.self_attn_fwd_bf16_blocked) on the same single planes.
         Head width below 64 (a multiple of 4): the same kernels, which are built for head width 64, on heads ZERO-PADDED to 64 columns
         -- one small bf16 product per head and per Q / K / V block writes its columns into a zeroed [M, 3 * heads * 64] planes matrix
         (zero columns add nothing to Q K^T and give zero context columns); a correct route for small test models, not a fast one.
@@ -408,7 +417,8 @@ class TransformerEncoder(nn.Module):
         x_p, qkv_p, o_p = ws.planes("x_p", M, E), ws.planes("qkv_p", M, 3 * E), ws.planes("o_p", M, E)
         x_b, qkv_b, o_b = x_p.buf[:M * E], qkv_p.buf[:M * 3 * E], o_p.buf[:M * E]
         t_b, ff_b = ws.planes("t_p", M, E).buf[:M * E], ws.planes("ff_p", M, F).buf[:M * F]
-        fast_attn = hd == 64 and L <= 288
+        fast_attn = hd == 64 and (L <= 288 or self.infer_attention_long)
+        attn_b1 = ops.self_attn_fwd_bf16 if L <= 288 else ops.self_attn_fwd_bf16_blocked
         h.copy_(emb.contiguous().view(M, E))
         scale = 1.0 / math.sqrt(float(hd))
         if not pre:
@@ -423,7 +433,7 @@ class TransformerEncoder(nn.Module):
                 return self._last_layer_first_token(ws, layer, w, h, None, seg, B, L, E, F, kv_p=kv_p)
             if fast_attn:
                 ops.gemm_bf16(x_b, w["wqkv"], None, M, 3 * E, E, bias=w["bqkv"], out_plane=qkv_b)
-                ops.self_attn_fwd_bf16(qkv_b, seg, batch=B, heads=H, L=L, head_dim=hd, scale=scale, out_plane=o_b)
+                attn_b1(qkv_b, seg, batch=B, heads=H, L=L, head_dim=hd, scale=scale, out_plane=o_b)
             elif hd != 64:
                 Ep, o32 = H * 64, ws.mat("bf16_o", M, E)
                 pad_p, pad_o = ws.planes("bf16_qkv_pad", M, 3 * Ep), ws.mat("bf16_o_pad", M, Ep)

@@ -2,7 +2,9 @@
 Prints ms per forward, algorithmic TFLOP/s (2MNK of the GEMMs + 4 L^2 d of attention) and a per-kernel-class breakdown
 from HIP events.  python tools/encoder_bench.py [--batch 32] [--iters 10] [--passes 3]
 --train [--precision mxfp8_train | bf16_train [--bf16-attention [--bf16-attention-long]]] [--recompute]: forward + backward per step, and
-the step's peak device memory.  --text-seq L / --only text | image: the text tower at another sequence length / one tower alone."""
+the step's peak device memory.  --text-seq L / --only text | image: the text tower at another sequence length / one tower alone.
+--ppo-shapes --precision bf16 | mxfp8 with --text-seq / --only: the per-tower loop on that inference schedule (forward_bf16 / forward_fp8);
+[--attention-long]: sequences longer than 288 on the key-blocked single-plane attention (TransformerEncoder.infer_attention_long)."""
 import argparse
 import os
 import sys
@@ -81,7 +83,8 @@ def measure_forward(batch_items=32, tags=2, n_img=16, iters=3, passes=3, dev=Non
             "mfma_issue_frac": round(passes * total_fl / total_ms / 1e9 / 2500.0, 4), "passes": passes, "precision": precision, "parts": parts}
 
 
-def main():
+def parse_args(argv=None):
+    """The command line, checked (argparse's error exit on a combination that means nothing); no device is touched."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--ppo-shapes", action="store_true", help="ViT over batch*16 frames, RoBERTa over batch*2 sequences")
@@ -102,15 +105,21 @@ def main():
     ap.add_argument("--bf16-attention-long", action="store_true",
                     help="--bf16-attention: sequences longer than 288 on the blocked single-plane kernels too "
                          "(TransformerEncoder.bf16_attention_long)")
+    ap.add_argument("--attention-long", action="store_true",
+                    help="--precision bf16 | mxfp8 (inference): sequences longer than 288 on the key-blocked single-plane attention "
+                         "(TransformerEncoder.infer_attention_long) instead of the 3-pass kernels")
     ap.add_argument("--text-seq", type=int, default=196, help="sequence length of the text tower (at most 514)")
     ap.add_argument("--only", choices=("both", "image", "text"), default="both", help="run one tower alone")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     if a.bf16_attention_long and not a.bf16_attention:
         ap.error("--bf16-attention-long is a switch of --bf16-attention")
     if not 1 <= a.text_seq <= ROBERTA["max_seq_length"]:
         ap.error("--text-seq: 1 .. %d" % ROBERTA["max_seq_length"])
-    if (a.text_seq != 196 or a.only != "both") and a.ppo_shapes and not a.train:
-        ap.error("--text-seq / --only are switches of the per-tower loop: not of --ppo-shapes without --train")
+    if a.attention_long and (a.train or a.precision not in ("bf16", "mxfp8")):
+        ap.error("--attention-long is a switch of the inference modes: give --precision bf16 | mxfp8, not --train")
+    if (a.text_seq != 196 or a.only != "both") and a.ppo_shapes and not a.train and a.precision not in ("bf16", "mxfp8"):
+        ap.error("--text-seq / --only are switches of the per-tower loop: not of --ppo-shapes without --train "
+                 "(--precision bf16 | mxfp8 excepted: they then run the per-tower loop on their own schedule)")
     if a.bf16_attention and not (a.train and a.precision == "bf16_train"):
         ap.error("--bf16-attention is a switch of --train --precision bf16_train")
     if a.recompute and not a.train:
@@ -119,14 +128,22 @@ def main():
         ap.error("--precision bf16_train is a training precision: give --train")
     if a.precision in ("bf16", "mxfp8") and (a.train or not a.ppo_shapes):
         ap.error("--precision bf16 / mxfp8 are inference modes: give --ppo-shapes, not --train")
+    return a
+
+
+def main():
+    a = parse_args()
     dev = torch.device("cuda:0")
     ops.set_gemm_passes(a.passes)
     torch.manual_seed(0)
-    if a.ppo_shapes and not a.train:
+    infer = a.precision if a.precision in ("bf16", "mxfp8") else None          # (parse_args: never with --train)
+    per_tower = infer is not None and (a.text_seq != 196 or a.only != "both" or a.attention_long)
+    if a.ppo_shapes and not a.train and not per_tower:
         prec = "split_bf16" if a.precision == "mxfp8_train" else a.precision      # (a training precision: ignored without --train)
         print(measure_forward(a.batch, iters=a.iters, passes=a.passes, dev=dev, precision=prec))
         return
     total_ms, total_fl = 0.0, 0.0
+    passes = 1 if infer else a.passes
     towers = [t for t in (("vit-b/16", VIT, 197), ("roberta-base", ROBERTA, a.text_seq))
               if a.only == "both" or t[0].startswith("vit") == (a.only == "image")]
     for name, cfg, L in towers:
@@ -142,6 +159,8 @@ def main():
         enc.bf16_attention = a.bf16_attention
         enc.bf16_attention_long = a.bf16_attention_long
         enc.recompute = a.recompute
+        enc.infer_attention_long = a.attention_long
+        infer_fwd = {"bf16": enc.forward_bf16, "mxfp8": enc.forward_fp8, None: enc}[infer]
         B = (a.batch * 16 if name.startswith("vit") else a.batch * 2) if a.ppo_shapes else a.batch
         emb = torch.randn(B, L, 768, device=dev, requires_grad=a.train)
         seg = torch.ones(B, L, dtype=torch.int64, device=dev)
@@ -152,7 +171,7 @@ def main():
                 enc(emb, seg).backward(dout)
             else:
                 with torch.no_grad():
-                    enc(emb, seg)
+                    infer_fwd(emb, seg)
         for _ in range(2):
             run()
         torch.cuda.synchronize()
@@ -176,8 +195,8 @@ def main():
         for k, v in prof.items():
             c = k.split("_")[0] + ("_" + k.split("_")[1] if k.startswith("gemm") else "")
             classes[c] = classes.get(c, 0.0) + v["ms"]
-        print(f"{name:13s} B={B} L={L} {a.precision if a.train else ''}: {ms:7.3f} ms/{'step' if a.train else 'forward'}  {fl / ms / 1e9:7.1f} TFLOP/s (algorithmic)  "
-              f"frac of 2.5 PF bf16 dense x{a.passes} passes: {a.passes * fl / ms / 1e9 / 2500:.3f}", flush=True)
+        print(f"{name:13s} B={B} L={L} {a.precision if a.train or infer else ''}{' attention-long' if a.attention_long else ''}: {ms:7.3f} ms/{'step' if a.train else 'forward'}  {fl / ms / 1e9:7.1f} TFLOP/s (algorithmic)  "
+              f"frac of 2.5 PF bf16 dense x{passes} passes: {passes * fl / ms / 1e9 / 2500:.3f}", flush=True)
         if a.train:
             print(f"    recompute {'on' if a.recompute else 'off'}: peak memory {peak / 2 ** 30:.2f} GiB ({(peak - resident) / 2 ** 30:.2f} GiB above "
                   f"the resident {resident / 2 ** 30:.2f}); saved activations by the formula {enc.saved_activation_bytes(B, L) / 2 ** 30:.2f} GiB",
@@ -188,7 +207,7 @@ def main():
                 tf = v["flops"] / (v["ms"] / v["n"]) / 1e9 if v["flops"] else 0.0
                 print(f"      {k:40s} n={v['n']:3d} avg {v['ms'] / v['n'] * 1e3:8.1f} us  {tf:7.1f} TFLOP/s", flush=True)
     print(f"dual encoder: {total_ms:.3f} ms  {total_fl / total_ms / 1e9:.1f} TFLOP/s algorithmic, "
-          f"MFMA issue fraction {a.passes * total_fl / total_ms / 1e9 / 2500:.3f}")
+          f"MFMA issue fraction {passes * total_fl / total_ms / 1e9 / 2500:.3f}")
 
 
 if __name__ == "__main__":
