@@ -24,7 +24,7 @@ extern "C" {
 #define LR2_ERR_SHAPE (-2)  /* shape not supported by the kernel's tiling */
 #define LR2_ERR_LAUNCH (-3) /* HIP launch failure */
 
-#define LR2_ABI_VERSION 25
+#define LR2_ABI_VERSION 26
 int lr2_abi_version(void);
 /* Fills name[0..len) with the HIP device name and returns the CU count (or <0). */
 int lr2_device_info(char* name, int len);
@@ -89,6 +89,12 @@ typedef struct lr2_epilogue {
  *   Supported: (fp32, fp32), (planes, planes), (planes A, fp32 B).  Planes are produced by the epilogue's out_hi,
  *   by lr2_split_planes(_multi) and by the LayerNorm / attention kernels' planes outputs.
  * a_bytes/b_bytes: bytes addressable from A/B, per plane (rows past the end read as zero: ragged M, ragged K in (1,1)).
+ *   In the (1,1) form the kernels never compare a row with K: the caller passes the extent of K ROWS (K * ld elements, or what is
+ *   addressable when that is less), not of the allocation -- rows K and later that lie inside a_bytes / b_bytes are added into the
+ *   product.  Whole rows: operands are read 16 bytes at a time and a load that crosses the extent reads as zero.
+ * LR2_ERR_ARG: act outside 0..2, act == 2 without aux_z.  LR2_ERR_SHAPE: a leading dimension smaller than the row it addresses
+ *   (lda < K, or < M when trans_a; ldb likewise; ld_out / ld_z / ld_resid / ld_aux / ld_planes < N when the pointer is set; ld_out
+ *   for adam_p) -- lr2_gemm_bf16 and lr2_gemm_bf16_train refuse the same.  Nothing is launched by a rejected call.
  * splits>1 uses split-K through splitk_ws (fp32 [splits][M][N]).  block_m: 128 or 64, or 256 = the 256 x 256 ping-pong kernel for
  *   planes x planes operands with passes = 3: the (0,0) form (whole 32-deep K steps, splits = 1) and the (1,1) form (any K, any
  *   splits: tiles x splits workgroups, the weight-gradient kernel of round 3); other combinations fall back to the 128-row family.
@@ -108,6 +114,10 @@ int lr2_gemm_row_split_plan(int M, int N, int K, int* rows_256, int* tail_block_
 /* Diagnostic: launches issued by lr2_gemm since the library was loaded -- counts[0] the 256 x 256 NT kernel, counts[1] its TN form,
  * counts[2] the general kernel family (tests assert which kernels a call reached; no device call). */
 int lr2_gemm_launch_counts(uint64_t counts[3]);
+/* Diagnostic (ABI 26): *rows = the tile height, 256 or 192, that the launchers of the 256 x 256 NT kernels (lr2_gemm, lr2_gemm_bf16,
+ * lr2_gemm_bf16_train at block_m == 256) pick for a launch of M rows and N columns: 192 when one round of 256-row tiles would leave
+ * CUs idle that a round of 192-row tiles fills.  Pure host arithmetic (no device call); tests assert which form a shape reaches. */
+int lr2_gemm256_tile_rows(int M, int N, int* rows);
 
 /* Row gather: dst[b, j, :] = src[b, index[b, j], :]  (rows of row_elems fp32; strides in elements).
  * replaces: text_emb[batch_index, index] / img_emb[batch_index, index] (finetune/ppo.py:268-271,321-324). */
@@ -433,7 +443,7 @@ int lr2_gemm_bf16_launch_counts(uint64_t counts[2]);
  *       and splits <= 1, following lr2_gemm_row_split_plan unless a dropout mask is fused (lr2_gemm's rule); else the general family at
  *       passes = 1 (block_m 128 / 64).  An input gradient runs in this form on the weight's transpose (lr2_split_planes_t).
  *   (1, 1):  C[M, N] = A[K, M]^T . B[K, N] -- the weight gradient dW[N_out, N_in] = dY[T, N_out]^T X[T, N_in] (M = N_out, N = N_in, K = T;
- *       any K: rows past a_bytes / b_bytes -- the EXACT plane extents -- read as zero).  Plain epilogue (alpha -> out).  colsum (with
+ *       any K: rows past a_bytes / b_bytes -- the extents of K WHOLE rows, lr2_gemm's rule -- read as zero).  Plain epilogue (alpha -> out).  colsum (with
  *       colsum_ws of max(128, splits * ceil(N / 256)) * M floats; M % 4 == 0): the bias gradient db[m] = sum_k A[k, m], the column sums
  *       of the bf16 plane AS THE PRODUCT SEES IT (not of the fp32 gradient it was rounded from).  block_m == 256: the 256 x 256
  *       single-pass TN kernel (csrc/gemm256_tn_b1.hip; 64-row K steps, tiles x splits workgroups, column sums from the same launch);
@@ -442,7 +452,7 @@ int lr2_gemm_bf16_launch_counts(uint64_t counts[2]);
  * LR2_ERR_ARG: NULL operands / epilogue / no output; act == 2 without aux_z; adam_p (no fused optimizer); accumulate or a training
  * epilogue (bias, act, dropout, resid, out_z, out_hi) with the (1,1) form; colsum with the (0,0) form or without colsum_ws; (1,0) / (0,1);
  * splits > 1 without splitk_ws or with act == 2.  LR2_ERR_SHAPE: lda / ldb % 8, N % 4, an epilogue leading dimension % 4, K % 64 in the (0,0) form,
- * M % 4 with colsum, a_bytes / b_bytes >= 4 GiB.  Nothing is launched by a rejected call.
+ * M % 4 with colsum, a_bytes / b_bytes >= 4 GiB, a leading dimension smaller than the row it addresses.  Nothing is launched by a rejected call.
  * replaces: nn.Linear forward and autograd's input / weight / bias gradients of it (tencentpretrain/layers/position_ffn.py:12-15,
  * multi_headed_attn.py:55-76) in that mode. */
 int lr2_gemm_bf16_train(const void* A, const void* B, int M, int N, int K, int lda, int ldb, int trans_a, int trans_b, uint64_t a_bytes,

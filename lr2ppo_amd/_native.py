@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(CSRC, "liblr2ppo_hip.so")
 SOURCES = ["gemm.hip", "gemm256.hip", "gemm256_mx.hip", "gemm256_b1.hip", "gemm256_tn_b1.hip", "norm.hip", "attn.hip", "selfattn_fwd.hip", "selfattn_bwd.hip", "first_token_attn.hip", "selfattn_mx.hip", "selfattn_mx_blocked.hip", "selfattn_b1_train.hip", "selfattn_b1_blocked.hip", "misc.hip", "fp8.hip", "fp8_train.hip"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "gemm256_ring.h"), os.path.join(CSRC, "fp8_common.h"), os.path.join(CSRC, "selfattn_common.h"), os.path.join(CSRC, "selfattn_b1.h"), os.path.join(INCLUDE, "lr2ppo_hip.h")]
 
-ABI_VERSION = 25     # == LR2_ABI_VERSION of include/lr2ppo_hip.h (tests assert the two agree)
+ABI_VERSION = 26     # == LR2_ABI_VERSION of include/lr2ppo_hip.h (tests assert the two agree)
 
 _lock = threading.Lock()
 _lib = None
@@ -97,6 +97,7 @@ SIGNATURES = {
     "lr2_gemm": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _U64, _U64, _I, _U64, _I, _U64, C.POINTER(Epilogue), _P, _I, _I, _I, _P],
     "lr2_gemm_row_split_plan": [_I, _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "lr2_gemm_launch_counts": [C.POINTER(C.c_uint64)],
+    "lr2_gemm256_tile_rows": [_I, _I, C.POINTER(C.c_int)],
     "lr2_gather_rows": [_P, _P, _P, _I, _I, _I, _U64, _U64, _U64, _P],
     "lr2_gather_rows_bwd": [_P, _P, _P, _I, _I, _I, _U64, _P],
     "lr2_copy_rows": [_P, _P, _I, _U64, _I, _I, _I, _U64, _U64, _P],

@@ -600,6 +600,7 @@ Epilogue to_device_epilogue(const lr2_epilogue* e) {
 }
 
 int launch_gemm256_nt(const GemmParams& p, hipStream_t stream);   // gemm256.hip
+int gemm256_nt_tile_rows(int M, int N);
 int launch_gemm256_tn(const GemmParams& p, int splits, hipStream_t stream);
 int launch_gemm256_b1(const GemmParams& p, hipStream_t stream);   // gemm256_b1.hip
 int launch_gemm256_b1_exact(const GemmParams& p, hipStream_t stream);
@@ -608,10 +609,25 @@ int launch_gemm256_tn_b1(const GemmParams& p, int splits, hipStream_t stream);  
 }  // namespace lr2gemm
 using namespace lr2gemm;
 
+// A leading dimension smaller than the row it addresses makes rows overlap (ld = 0, a zeroed epilogue struct, overlaps all of them):
+// refused by all three entry points.  Operands: lda >= K ([M][K]) or >= M ([K][M]), likewise ldb; every epilogue tensor whose pointer
+// is set: ld >= N (the fused optimizer step addresses adam_p / m / v with ld_out).
+static bool gemm_ld_too_small(const lr2_epilogue* e, int M, int N, int K, int lda, int ldb, int trans_a, int trans_b) {
+  if (lda < (trans_a ? M : K) || ldb < (trans_b ? N : K)) return true;
+  return ((e->out || e->adam_p) && e->ld_out < N) || (e->out_z && e->ld_z < N) || (e->resid && e->ld_resid < N) ||
+         (e->aux_z && e->ld_aux < N) || (e->out_hi && e->ld_planes < N);
+}
+
 static uint64_t g_launches[3] = {0, 0, 0};     // 256 NT, 256 TN, general family (host-side counters: lr2_gemm_launch_counts)
 extern "C" int lr2_gemm_launch_counts(uint64_t counts[3]) {
   if (!counts) return LR2_ERR_ARG;
   for (int i = 0; i < 3; ++i) counts[i] = g_launches[i];
+  return 0;
+}
+
+extern "C" int lr2_gemm256_tile_rows(int M, int N, int* rows) {
+  if (!rows || M <= 0 || N <= 0) return LR2_ERR_ARG;
+  *rows = gemm256_nt_tile_rows(M, N);
   return 0;
 }
 
@@ -641,6 +657,8 @@ extern "C" int lr2_gemm(const void* A, const void* B, int M, int N, int K, int l
   if (!A || !B || M <= 0 || N <= 0 || K <= 0 || !epi || (!epi->out && !epi->out_hi && !epi->adam_p)) return LR2_ERR_ARG;
   if (epi->adam_p && (!epi->adam_m || !epi->adam_v || epi->out || epi->out_hi || epi->ld_out % 4)) return LR2_ERR_ARG;
   if (passes != 1 && passes != 3) return LR2_ERR_ARG;
+  if (trans_a && !trans_b) return LR2_ERR_ARG;   // (1,0) is not a form the path needs (refused here, before a launch is counted)
+  if (epi->act < 0 || epi->act > 2 || (epi->act == 2 && !epi->aux_z)) return LR2_ERR_ARG;   // GELU' needs its input
   if (epi->drop_seed_dev && epi->drop_site >= 65536u) return LR2_ERR_ARG;      // the site travels in 16 bits beside the threshold
   if (epi->adam_p && epi->drop_p > 0.f) return LR2_ERR_ARG;                    // the update consumes the result: nothing to mask
   if (epi->colsum && (!trans_a || !trans_b || !epi->colsum_ws || (M % 4))) return LR2_ERR_ARG;   // weight-gradient form only
@@ -665,6 +683,7 @@ extern "C" int lr2_gemm(const void* A, const void* B, int M, int N, int K, int l
   if ((epi->out && epi->ld_out % 4) || (epi->out_z && epi->ld_z % 4) || (epi->resid && epi->ld_resid % 4) ||
       (epi->aux_z && epi->ld_aux % 4) || (epi->out_hi && epi->ld_planes % 4))
     return LR2_ERR_SHAPE;
+  if (gemm_ld_too_small(epi, M, N, K, lda, ldb, trans_a, trans_b)) return LR2_ERR_SHAPE;
   if (a_bytes >= (1ull << 32) || b_bytes >= (1ull << 32) || a_lo_off >= (1ull << 32) || b_lo_off >= (1ull << 32))
     return LR2_ERR_SHAPE;
   if (!a_planes && b_planes) return LR2_ERR_ARG;  // (fp32 A, planes B) is not a combination the path needs
@@ -776,6 +795,7 @@ extern "C" int lr2_gemm_bf16(const void* A, const void* B, int M, int N, int K, 
   if (K % 64) return LR2_ERR_SHAPE;             // whole 64-deep K steps on the 256 x 256 kernel AND on the 128- / 64-row family
   if ((lda % 8) || (ldb % 8) || (N % 4)) return LR2_ERR_SHAPE;
   if ((epi->out && epi->ld_out % 4) || (epi->resid && epi->ld_resid % 4) || (epi->out_hi && epi->ld_planes % 4)) return LR2_ERR_SHAPE;
+  if (gemm_ld_too_small(epi, M, N, K, lda, ldb, 0, 0)) return LR2_ERR_SHAPE;
   if (a_bytes >= (1ull << 32) || b_bytes >= (1ull << 32)) return LR2_ERR_SHAPE;
   const bool use256 = block_m == 256 && a_bytes <= 0xFFFFFD00ull && b_bytes <= 0xFFFFFD00ull;
   if (block_m != 64) block_m = 128;
@@ -848,6 +868,7 @@ extern "C" int lr2_gemm_bf16_train(const void* A, const void* B, int M, int N, i
   if ((epi->out && epi->ld_out % 4) || (epi->out_z && epi->ld_z % 4) || (epi->resid && epi->ld_resid % 4) ||
       (epi->aux_z && epi->ld_aux % 4) || (epi->out_hi && epi->ld_planes % 4))
     return LR2_ERR_SHAPE;
+  if (gemm_ld_too_small(epi, M, N, K, lda, ldb, tn, tn)) return LR2_ERR_SHAPE;
   if (a_bytes >= (1ull << 32) || b_bytes >= (1ull << 32)) return LR2_ERR_SHAPE;
   const bool fits256 = block_m == 256 && a_bytes <= 0xFFFFFD00ull && b_bytes <= 0xFFFFFD00ull;
   const bool use256nt = fits256 && !tn && splits <= 1 &&

@@ -409,6 +409,12 @@ def gemm(a, b, out: Optional[torch.Tensor], M: int, N: int, K: int, *, trans_a=F
         e.colsum, e.colsum_ws = colsum.data_ptr(), colsum_ws.data_ptr()
     a_bytes = a.plane_bytes() if a_pl else a.numel() * 4
     b_bytes = b.plane_bytes() if b_pl else b.numel() * 4
+    if trans_a and trans_b:
+        # the kernels never compare a row with K: rows past it read as zero only because the extent ends there, so an operand that is
+        # the first K rows of a taller buffer (a workspace, a Planes view) passes the extent of K rows, not of the allocation.  Whole
+        # rows: an extent that ends inside a 16-byte load of row K - 1 would zero that row's last columns.
+        a_bytes = min(a_bytes, K * lda * (2 if a_pl else 4))
+        b_bytes = min(b_bytes, K * ldb * (2 if b_pl else 4))
     args = (a.data_ptr(), b.data_ptr(), M, N, K, lda, ldb, 1 if trans_a else 0, 1 if trans_b else 0, a_bytes, b_bytes,
             1 if a_pl else 0, a.lo_off * 2 if a_pl else 0, 1 if b_pl else 0, b.lo_off * 2 if b_pl else 0, C.byref(e),
             _ptr(splitk_ws), sp, bm, passes or _PASSES, _stream())
@@ -594,9 +600,11 @@ def gemm_bf16_train(a, b, out: Optional[torch.Tensor], M: int, N: int, K: int, *
     if ldb is None:
         ldb = N if trans else K
     if trans:
-        a_ptr, _ = _one_plane(a, (K - 1) * lda + M, "gemm_bf16_train: a")
-        b_ptr, _ = _one_plane(b, (K - 1) * ldb + N, "gemm_bf16_train: b")
-        a_n, b_n = (K - 1) * lda + M, (K - 1) * ldb + N             # the EXACT extents: rows >= K read as zero
+        a_ptr, a_n = _one_plane(a, (K - 1) * lda + M, "gemm_bf16_train: a")
+        b_ptr, b_n = _one_plane(b, (K - 1) * ldb + N, "gemm_bf16_train: b")
+        # the extents of K WHOLE rows: rows >= K read as zero.  (Not (K - 1) * ld + M: an extent that ends inside a 16-byte load zeroes
+        # the last columns of row K - 1 whenever M or N is no multiple of 8.)
+        a_n, b_n = min(a_n, K * lda), min(b_n, K * ldb)
         if block_m is None or splits is None:
             bm, sp = bf16_train_tn_tiling(M, N, K)
             block_m = bm if block_m is None else block_m
