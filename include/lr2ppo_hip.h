@@ -24,7 +24,7 @@ extern "C" {
 #define LR2_ERR_SHAPE (-2)  /* shape not supported by the kernel's tiling */
 #define LR2_ERR_LAUNCH (-3) /* HIP launch failure */
 
-#define LR2_ABI_VERSION 26
+#define LR2_ABI_VERSION 27
 int lr2_abi_version(void);
 /* Fills name[0..len) with the HIP device name and returns the CU count (or <0). */
 int lr2_device_info(char* name, int len);
@@ -549,6 +549,47 @@ int lr2_self_attn_fwd_bf16_blocked(const void* q, const void* k, const void* v, 
  * synchronised).  LR2_ERR_ARG for a NULL count.
  * replaces: nothing (a test hook, as lr2_self_attn_bf16_blocked_launch_counts: which attention a schedule ran). */
 int lr2_self_attn_fwd_bf16_blocked_launch_count(uint64_t* count);
+
+/* ABI 27.  The single-pass f16 inference mode (FeatureExtractor(precision="f16")): the "bf16" mode's entry points with
+ * every single plane in IEEE binary16 -- 11 significand bits per operand instead of 8, the same bytes, the same matrix rate
+ * (v_mfma_f32_16x16x32_f16).  NOT the parity path.  An f16 plane is written by ONE rule everywhere: clamp to +-65504 (an outlier
+ * saturates, it does not become inf), round to nearest even, NaN stays NaN, results below 2^-14 are IEEE subnormals.
+ *
+ * lr2_gemm_f16: C[M, N] = A[M, K] . B[N, K]^T with A and B ONE f16 plane each (row strides lda / ldb elements, a_bytes / b_bytes
+ * addressable from each pointer: rows past the end read as zero), fp32 accumulate; lr2_gemm_bf16's inference contract: alpha, bias,
+ * act 0 / 1 (GELU), resid; the result goes to out (fp32) and / or out_hi -- ONE f16 plane when out_lo_off == 0, bf16 hi / lo planes (as
+ * ever: the operands of lr2_self_attn_fwd) otherwise.  It runs on the 256 x 256 kernel of csrc/gemm256_f16.hip (the tile rule of
+ * lr2_gemm256_tile_rows) at every size.  LR2_ERR_ARG: NULL operands / epilogue, no destination, dropout, act 2, accumulate, out_z, the
+ * fused optimizer step, column sums.  LR2_ERR_SHAPE: K % 64, lda / ldb % 8, N % 4, an epilogue leading dimension % 4 or smaller than N,
+ * lda / ldb < K, a_bytes / b_bytes > 4 GiB - 768 B.  Nothing is launched (and nothing counted) by a rejected call.
+ * replaces: nn.Linear forward (tencentpretrain/layers/position_ffn.py:12-15, multi_headed_attn.py:55-76) in that mode. */
+int lr2_gemm_f16(const void* A, const void* B, int M, int N, int K, int lda, int ldb, uint64_t a_bytes, uint64_t b_bytes,
+                 const lr2_epilogue* epi, void* stream);
+/* Diagnostic: *count = accepted lr2_gemm_f16 calls since the library was loaded (a plain host counter, not synchronised).
+ * replaces: nothing (a test hook, as lr2_gemm_bf16_launch_counts). */
+int lr2_gemm_f16_launch_count(uint64_t* count);
+/* lr2_layernorm_fwd with the single plane in f16: the arguments of its out_lo_off = 0 form (out fp32 and / or out_f16, optional mean /
+ * rstd, mode 0 = nn.LayerNorm / 1 = the TencentPretrain LayerNorm, the group / group_stride row map).  D % 4 == 0, D <= 1024.
+ * replaces: tencentpretrain/layers/layer_norm.py:5-21 (and nn.LayerNorm, finetune/xit.py:37) in front of a product of that mode. */
+int lr2_layernorm_fwd_f16(const void* x, const void* gamma, const void* beta, void* out, void* out_f16, void* mean, void* rstd, int rows,
+                          int D, float eps, int mode, int group, uint64_t group_stride, void* stream);
+/* dst[i] = f16(src[i]), n fp32 elements -> ONE f16 plane by the rule above: the mode's weights (once per weight refresh), its post-LN
+ * first-layer operand, the context of its fallback attention.  n % 4 == 0; src 16-byte, dst 8-byte aligned (else LR2_ERR_SHAPE).
+ * replaces: the .half() casts of the 16-bit configuration (BASELINE.json configs[2]; tencentpretrain/utils/ has no kernel of its own). */
+int lr2_round_f16(const void* src, void* dst, uint64_t n, void* stream);
+/* lr2_self_attn_fwd_bf16 on f16 planes (csrc/selfattn_f16.hip): q / k / v ONE f16 plane each (row stride ld elements; the three column
+ * blocks of the [rows, 3E] plane lr2_gemm_f16 writes), S and O on the f16 MFMA, fp32 softmax with the row sum of the unrounded
+ * probabilities, the un-normalised probabilities rounded to f16 as the A operand of P V, key mask -10000 * (seg <= 0) after the scale;
+ * the context rows leave as fp32 (o_f32 [batch * L, ld_o]) and / or as ONE f16 plane (o_f16 [batch * L, ld_o]: the A operand of
+ * lr2_gemm_f16).  No MX-FP8 outputs.  One workgroup per (sequence, head), or persistent workgroups under lr2_self_attn_fwd_bf16_plan's
+ * rule.  head_dim 64, 1 <= L <= 288, inference only.  LR2_ERR_ARG: a NULL q / k / v / seg, no output, batch / heads / L <= 0.
+ * LR2_ERR_SHAPE: head_dim != 64, L > 288, ld % 8, ld or ld_o below heads * 64, ld_o % 4.  Nothing is launched by a rejected call.
+ * replaces: tencentpretrain/layers/multi_headed_attn.py:60-74 in that mode. */
+int lr2_self_attn_fwd_f16(const void* q, const void* k, const void* v, int ld, const int64_t* seg, void* o_f32, void* o_f16, int ld_o,
+                          int batch, int heads, int L, int head_dim, float scale, void* stream);
+/* Diagnostic: *count = accepted lr2_self_attn_fwd_f16 calls since the library was loaded.
+ * replaces: nothing (a test hook, as lr2_self_attn_fwd_bf16_blocked_launch_count: which attention a schedule ran). */
+int lr2_self_attn_fwd_f16_launch_count(uint64_t* count);
 
 /* ABI 20.  MX-FP8 encoder training (FeatureExtractor(precision="mxfp8_train")): the backward's operands, blocked along the axis its
  * products reduce over, and a K-sliced weight-gradient product.

@@ -163,6 +163,27 @@ __device__ __forceinline__ void store_planes4(bf16_t* p, size_t lo_off, float4 v
   *reinterpret_cast<u32x2_t*>(p + lo_off) = lv;
 }
 
+// ---- the f16 plane writer (the "f16" inference mode: lr2_gemm_f16, lr2_layernorm_fwd_f16, lr2_round_f16, lr2_self_attn_fwd_f16) ----
+// fp32 -> IEEE binary16 bits, round to nearest even (the plain conversion: v_cvt_pk_f16_f32; never the pkrtz builtin, which truncates).
+// The value is clamped to +-65504 first (v_med3_f32), so an outlier saturates instead of becoming inf -- and NaN one softmax later; NaN
+// stays NaN (the median of a NaN is a number: the select puts it back); results below 2^-14 leave as f16 subnormals.
+typedef uint16_t f16_t;   // raw binary16 bits in HBM / LDS
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
+typedef __attribute__((ext_vector_type(2))) _Float16 f16x2_t;
+__device__ __forceinline__ float f16_clamp(float x) {
+  const float c = __builtin_amdgcn_fmed3f(x, -65504.0f, 65504.0f);
+  return x != x ? x : c;
+}
+// two fp32 -> packed f16 pair (low half = a)
+__device__ __forceinline__ uint32_t cvt_pk_f16(float a, float b) {
+  f32x2_t v = {f16_clamp(a), f16_clamp(b)};
+  f16x2_t r = __builtin_convertvector(v, f16x2_t);
+  return __builtin_bit_cast(uint32_t, r);
+}
+__device__ __forceinline__ u32x2_t f16_pack4(float4 v) { return u32x2_t{cvt_pk_f16(v.x, v.y), cvt_pk_f16(v.z, v.w)}; }
+// four fp32 -> four f16, one 8-byte store: a SINGLE f16 plane
+__device__ __forceinline__ void store_f16x4(f16_t* p, float4 v) { *reinterpret_cast<u32x2_t*>(p) = f16_pack4(v); }
+
 // ---------------------------------------------------------------------------------------------
 // Fused GEMM epilogue description (shared by the MFMA kernel and the split-K reducer); see gemm.hip::epilogue_vec4.
 // ---------------------------------------------------------------------------------------------

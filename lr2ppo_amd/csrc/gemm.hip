@@ -604,6 +604,7 @@ int gemm256_nt_tile_rows(int M, int N);
 int launch_gemm256_tn(const GemmParams& p, int splits, hipStream_t stream);
 int launch_gemm256_b1(const GemmParams& p, hipStream_t stream);   // gemm256_b1.hip
 int launch_gemm256_b1_exact(const GemmParams& p, hipStream_t stream);
+int launch_gemm256_f16(const GemmParams& p, hipStream_t stream);   // gemm256_f16.hip
 int launch_gemm256_tn_b1(const GemmParams& p, int splits, hipStream_t stream);   // gemm256_tn_b1.hip
 
 }  // namespace lr2gemm
@@ -838,6 +839,41 @@ extern "C" int lr2_gemm_bf16(const void* A, const void* B, int M, int N, int K, 
   }
   ++g_launches_b1[0];
   return launch_gemm256_b1(p, s);
+}
+
+// ---- single-pass f16 products of ONE plane per operand (the "f16" inference mode): the 256 x 256 kernel of gemm256_f16.hip at every size ----
+static uint64_t g_launches_f16 = 0;
+extern "C" int lr2_gemm_f16_launch_count(uint64_t* count) {
+  if (!count) return LR2_ERR_ARG;
+  *count = g_launches_f16;
+  return 0;
+}
+
+extern "C" int lr2_gemm_f16(const void* A, const void* B, int M, int N, int K, int lda, int ldb, uint64_t a_bytes, uint64_t b_bytes,
+                            const lr2_epilogue* epi, void* stream) {
+  if (!A || !B || M <= 0 || N <= 0 || K <= 0 || !epi || (!epi->out && !epi->out_hi)) return LR2_ERR_ARG;
+  // lr2_gemm_bf16's inference contract: no dropout, no GELU', no accumulate, no kept pre-activation, no fused optimizer, no column sums
+  if (epi->drop_p > 0.f || epi->act < 0 || epi->act > 1 || epi->accumulate || epi->out_z || epi->adam_p || epi->colsum) return LR2_ERR_ARG;
+  if (K % 64) return LR2_ERR_SHAPE;             // whole 64-deep K steps
+  if ((lda % 8) || (ldb % 8) || (N % 4)) return LR2_ERR_SHAPE;
+  if ((epi->out && epi->ld_out % 4) || (epi->resid && epi->ld_resid % 4) || (epi->out_hi && epi->ld_planes % 4)) return LR2_ERR_SHAPE;
+  if (gemm_ld_too_small(epi, M, N, K, lda, ldb, 0, 0)) return LR2_ERR_SHAPE;
+  if (a_bytes > 0xFFFFFD00ull || b_bytes > 0xFFFFFD00ull) return LR2_ERR_SHAPE;     // the ring's 32-bit source offsets; no other f16 kernel
+  GemmParams p{};
+  p.A = A;
+  p.B = B;
+  p.M = M;
+  p.N = N;
+  p.K = K;
+  p.lda = lda;
+  p.ldb = ldb;
+  p.a_bytes = (uint32_t)a_bytes;
+  p.b_bytes = (uint32_t)b_bytes;
+  p.k_tiles_per_split = K / 64;
+  p.epi = to_device_epilogue(epi);
+  p.epi.store_nt = (uint64_t)M * (uint64_t)N * (epi->out ? 4ull : 2ull) >= (256ull << 20) ? 1 : 0;   // lr2_gemm_bf16's rule
+  ++g_launches_f16;
+  return launch_gemm256_f16(p, (hipStream_t)stream);
 }
 
 // ---- single-pass bf16 products of encoder training (the "bf16_train" mode): forward / input gradient (NT) and weight gradient (TN) ----

@@ -1,5 +1,5 @@
 // The LDS ring of the 256 x 256 "ping-pong" NT products -- gemm256.hip (split-bf16), gemm256_b1.hip (single-pass bf16),
-// gemm256_mx.hip (MX-FP8): geometry, lane set-up, DMA issue, fragment reads, the section waits, prologue and drain, once.  A kernel file keeps what
+// gemm256_f16.hip (single-pass f16), gemm256_mx.hip (MX-FP8): geometry, lane set-up, DMA issue, fragment reads, the section waits, prologue and drain, once.  A kernel file keeps what
 // its operand format differs in: the MFMA section, the epilogue, the launcher (and, for MX-FP8, the scales and its own K step).
 //
 // Structure (CDNA4, one workgroup of 8 waves per CU, 128 KiB of LDS):

@@ -134,7 +134,8 @@ __device__ __forceinline__ float mul_gelu_grad_exact(float x, float z) {
   return (float)((double)x * g);
 }
 // EXACT (kernels instantiated for lr2_gemm_bf16_train only): act == 2 multiplies by mul_gelu_grad_exact
-template <int NS, bool EXACT = false>
+// F16 (kernels instantiated for lr2_gemm_f16 only): the single plane (lo_off == 0) is an f16 plane (common.h::f16_pack4)
+template <int NS, bool EXACT = false, bool F16 = false>
 __device__ __forceinline__ void epilogue_apply4(const Epilogue& e, float4 v, float4 b, const EpiLoads<NS>& L, int m, int n, int N) {
 #pragma clang fp contract(off)      // one rounding per written operation, whatever path forms the element (see epilogue_fast)
   constexpr int SR = NS == 3 ? 1 : 0, SO = NS == 3 ? 2 : 0;
@@ -175,7 +176,10 @@ const float adam_lr = e.lr_dev ? scalar_load_f32((const float*)e.dev_scalar) : e
   }
   if (e.out_hi) {  // bf16 hi/lo planes for the next GEMM (same bytes as the fp32 tensor they replace)
     u32x2_t hv, lv;
-    split4(v, hv, lv);
+    bool one_f16 = false;
+    if constexpr (F16) one_f16 = e.lo_off == 0;
+    if (one_f16) hv = f16_pack4(v);
+    else split4(v, hv, lv);
     bf16_t* ph = e.out_hi + (size_t)m * e.ld_planes + n;
     // lo_off == 0: ONE bf16 plane (hi == the value rounded to nearest even) -- lr2_gemm_bf16's operand format; no lo store
     if (e.store_nt) {
@@ -272,7 +276,8 @@ __device__ __forceinline__ void epilogue_to_slab(f32x4_t (&acc)[MI][NI], float* 
 //   ACT 0 / 1 (GELU; Z: store the pre-activation) / 2 (multiply by GELU'(aux));  DROP: mask after the activation;
 //   RESID: add the residual row;  OUT: fp32 result;  PL: bf16 hi / lo planes result;  NT: non-temporal stores.
 //   LO (with PL): the lo plane is stored too; false = ONE bf16 plane (Epilogue::lo_off == 0, the single-pass bf16 mode).
-template <int NP, int RPP, int NS, int ACT, bool Z, bool DROP, bool RESID, bool OUT, bool PL, bool NT, bool LO = true>
+//   F16 (with PL, !LO): that one plane is an f16 plane (the "f16" mode, gemm256_f16.hip).
+template <int NP, int RPP, int NS, int ACT, bool Z, bool DROP, bool RESID, bool OUT, bool PL, bool NT, bool LO = true, bool F16 = false>
 __device__ __forceinline__ void epilogue_fast(const Epilogue& e, const float4 (&v)[NP], float4 b, const EpiLoads<NS> (&L)[NP],
                                               int m0, int n, int N) {
 #pragma clang fp contract(off)
@@ -305,7 +310,8 @@ __device__ __forceinline__ void epilogue_fast(const Epilogue& e, const float4 (&
     }
     if constexpr (PL) {
       u32x2_t hv, lv;
-      split4(x, hv, lv);
+      if constexpr (F16 && !LO) hv = f16_pack4(x);
+      else split4(x, hv, lv);
       bf16_t* p = e.out_hi + (size_t)m * e.ld_planes + n;
       if constexpr (NT) {
         __builtin_nontemporal_store(hv, reinterpret_cast<u32x2_t*>(p));
@@ -321,8 +327,8 @@ __device__ __forceinline__ void epilogue_fast(const Epilogue& e, const float4 (&
 // -> true when one of the instantiated forms took the slab.  WIDE 2: the full list (the 256 x 256 kernels, where the encoders'
 // training products run); 1: the 8-wave kernels (the heads' M = 12 544 products); 0: the other planes x planes kernels of the general
 // family, the inference forms only; -1: none (fifty kernel instantiations: compile time); 3: the single-pass bf16 kernel
-// (gemm256_b1.hip): the inference forms with ONE bf16 plane or hi / lo planes.
-template <int NP, int RPP, int NS, int WIDE>
+// (gemm256_b1.hip, gemm256_f16.hip): the inference forms with ONE bf16 (F16: f16) plane or hi / lo planes.
+template <int NP, int RPP, int NS, int WIDE, bool F16 = false>
 __device__ __forceinline__ bool epilogue_fast_dispatch(const Epilogue& e, const float4 (&v)[NP], float4 b,
                                                        const EpiLoads<NS> (&L)[NP], int m0, int n, int N) {
   if constexpr (WIDE < 0) return false;        // kernels with an fp32 operand: HBM-bound weight streams, the epilogue is not their cost
@@ -334,11 +340,11 @@ __device__ __forceinline__ bool epilogue_fast_dispatch(const Epilogue& e, const 
   const bool one_plane = pl && e.lo_off == 0;
   if constexpr (WIDE == 3) {
     if (z || drop || act > 1) return false;
-#define LR2_FAST1(ACT, RESID, OUT, PL, LO)                                                                             \
-  if (act == ACT && resid == RESID && out == OUT && pl == PL && one_plane == (PL && !LO)) {                           \
-    if (e.store_nt) epilogue_fast<NP, RPP, NS, ACT, false, false, RESID, OUT, PL, true, LO>(e, v, b, L, m0, n, N);    \
-    else epilogue_fast<NP, RPP, NS, ACT, false, false, RESID, OUT, PL, false, LO>(e, v, b, L, m0, n, N);               \
-    return true;                                                                                                     \
+#define LR2_FAST1(ACT, RESID, OUT, PL, LO)                                                                                  \
+  if (act == ACT && resid == RESID && out == OUT && pl == PL && one_plane == (PL && !LO)) {                                \
+    if (e.store_nt) epilogue_fast<NP, RPP, NS, ACT, false, false, RESID, OUT, PL, true, LO, F16>(e, v, b, L, m0, n, N);    \
+    else epilogue_fast<NP, RPP, NS, ACT, false, false, RESID, OUT, PL, false, LO, F16>(e, v, b, L, m0, n, N);              \
+    return true;                                                                                                          \
   }
     LR2_FAST1(0, false, false, true, false)     // bias -> one plane (QKV)
     LR2_FAST1(1, false, false, true, false)     // bias, GELU -> one plane (FFN-1)
@@ -373,7 +379,7 @@ __device__ __forceinline__ bool epilogue_fast_dispatch(const Epilogue& e, const 
   return false;
 }
 
-template <int WN, int HALF, int NS, int WIDE, bool EXACT = false>
+template <int WN, int HALF, int NS, int WIDE, bool EXACT = false, bool F16 = false>
 __device__ __forceinline__ void epilogue_from_slab(const GemmParams& g, float* slab, int mw, int nw, int lane, float* partial,
                                                    float4 bias4, const EpiSlab<WN, NS>& S) {
   constexpr int LDW = WN + 4;
@@ -389,9 +395,9 @@ __device__ __forceinline__ void epilogue_from_slab(const GemmParams& g, float* s
   // (LR2_GEMM_EPI_GENERAL=1 switches the fast forms off: tools/dbg/fuzz_epilogue.py compares the two paths bit for bit)
   if (!partial && !g.epi_general && mw + 32 * HALF + 32 <= g.M && nw + WN <= g.N) {   // wave-uniform: the slab lies inside the matrix
     if constexpr (EXACT) {      // (the straight-line forms multiply by gelu_erf_grad)
-      if (g.epi.act != 2 && epilogue_fast_dispatch<NP, RPP, NS, WIDE>(g.epi, v, bias4, S.L, mw + 32 * HALF + row0, n, g.N)) return;
+      if (g.epi.act != 2 && epilogue_fast_dispatch<NP, RPP, NS, WIDE, F16>(g.epi, v, bias4, S.L, mw + 32 * HALF + row0, n, g.N)) return;
     } else {
-      if (epilogue_fast_dispatch<NP, RPP, NS, WIDE>(g.epi, v, bias4, S.L, mw + 32 * HALF + row0, n, g.N)) return;
+      if (epilogue_fast_dispatch<NP, RPP, NS, WIDE, F16>(g.epi, v, bias4, S.L, mw + 32 * HALF + row0, n, g.N)) return;
     }
   }
 #pragma unroll
@@ -399,7 +405,7 @@ __device__ __forceinline__ void epilogue_from_slab(const GemmParams& g, float* s
     const int m = mw + 32 * HALF + pass * RPP + row0;
     if (m < g.M && n < g.N) {
       if (partial) st4(partial + (size_t)m * g.N + n, v[pass]);
-      else epilogue_apply4<NS, EXACT>(g.epi, v[pass], bias4, S.L[pass], m, n, g.N);
+      else epilogue_apply4<NS, EXACT, F16>(g.epi, v[pass], bias4, S.L[pass], m, n, g.N);
     }
   }
 }
@@ -407,7 +413,7 @@ __device__ __forceinline__ void epilogue_from_slab(const GemmParams& g, float* s
 // PIPE: request slab h+1's HBM operands before slab h's stores (after slab h's accumulators have moved to LDS, so the
 // register peak is acc - 32 + 3 x 32 for NS = 1).  Kernels that keep up to three requests per element (NS = 3) and run
 // several workgroups per CU request per slab instead: their register budget decides their occupancy.
-template <int WM, int WN, int MI, int NI, int NS, int HALF, bool PIPE, int WIDE, bool EXACT = false>
+template <int WM, int WN, int MI, int NI, int NS, int HALF, bool PIPE, int WIDE, bool EXACT = false, bool F16 = false>
 __device__ __forceinline__ void epilogue_pipeline(const GemmParams& g, f32x4_t (&acc)[MI][NI], float* slab, int mw, int nw,
                                                   int lane, float* partial, float4 bias4, EpiSlab<WN, NS>& cur) {
   if constexpr (!PIPE) {
@@ -418,12 +424,12 @@ __device__ __forceinline__ void epilogue_pipeline(const GemmParams& g, f32x4_t (
   if constexpr (PIPE && HALF + 1 < WM / 32) {
     if (!partial) epilogue_request<WN, NS, HALF + 1>(g, next, mw, nw, lane);
   }
-  epilogue_from_slab<WN, HALF, NS, WIDE, EXACT>(g, slab, mw, nw, lane, partial, bias4, cur);
+  epilogue_from_slab<WN, HALF, NS, WIDE, EXACT, F16>(g, slab, mw, nw, lane, partial, bias4, cur);
   if constexpr (HALF + 1 < WM / 32)
-    epilogue_pipeline<WM, WN, MI, NI, NS, HALF + 1, PIPE, WIDE, EXACT>(g, acc, slab, mw, nw, lane, partial, bias4, PIPE ? next : cur);
+    epilogue_pipeline<WM, WN, MI, NI, NS, HALF + 1, PIPE, WIDE, EXACT, F16>(g, acc, slab, mw, nw, lane, partial, bias4, PIPE ? next : cur);
 }
 
-template <int WM, int WN, int MI, int NI, int NS = 3, int WIDE = (NS == 1 ? 2 : 0), bool EXACT = false>
+template <int WM, int WN, int MI, int NI, int NS = 3, int WIDE = (NS == 1 ? 2 : 0), bool EXACT = false, bool F16 = false>
 __device__ __forceinline__ void epilogue_wave(const GemmParams& g, f32x4_t (&acc)[MI][NI], float* slab, int mw, int nw,
                                               int lane, float* partial) {
   static_assert(WM == 32 || WM == 64 || WM == 96 || WM == 128, "wave tile rows");
@@ -440,7 +446,7 @@ __device__ __forceinline__ void epilogue_wave(const GemmParams& g, f32x4_t (&acc
   // them -- and with loads and stores on one in-order counter the only wait it can write there is vmcnt(0): every slab waited for
   // the stores of the slab before it, one HBM write latency each (12 us of a 67-us K = 768 tile, profiles/experiments/README.md E).
   asm volatile("" ::"v"(bias4.x), "v"(bias4.y), "v"(bias4.z), "v"(bias4.w));
-  epilogue_pipeline<WM, WN, MI, NI, NS, 0, PIPE, WIDE, EXACT>(g, acc, slab, mw, nw, lane, partial, bias4, first);
+  epilogue_pipeline<WM, WN, MI, NI, NS, 0, PIPE, WIDE, EXACT, F16>(g, acc, slab, mw, nw, lane, partial, bias4, first);
 }
 
 // Fused AdamW epilogue: the weight, exp_avg and exp_avg_sq vectors of all 32 rows of a slab are requested BEFORE the

@@ -62,6 +62,13 @@ __global__ __launch_bounds__(256) void split_planes_kernel(const float* __restri
     store_planes4(dst + i * 4, lo_off, reinterpret_cast<const float4*>(src)[i]);
 }
 
+// fp32 -> ONE f16 plane (common.h's f16 plane writer: clamp to +-65504, round to nearest even): the "f16" inference mode's weights,
+// its post-LN first-layer operand and the context of its fallback attention
+__global__ __launch_bounds__(256) void round_f16_kernel(const float* __restrict__ src, f16_t* __restrict__ dst, size_t n4) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256)
+    store_f16x4(dst + i * 4, reinterpret_cast<const float4*>(src)[i]);
+}
+
 // planes of dropout_mask(src) / (1 - p): the gradient entering a dropped branch (pre-LN encoder layers)
 __global__ __launch_bounds__(256) void dropout_planes_kernel(const float* __restrict__ src, bf16_t* __restrict__ dst,
                                                              size_t lo_off, size_t n4, float scale, uint32_t thr, uint64_t key) {
@@ -884,6 +891,15 @@ extern "C" int lr2_split_planes(const void* src, void* dst_hi, uint64_t lo_off, 
   if (misaligned(src, 16) || misaligned(dst_hi, 8)) return LR2_ERR_SHAPE;       // float4 loads, 4 x bf16 stores per plane
   LR2_LAUNCH(split_planes_kernel, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, (const float*)src,
              (bf16_t*)dst_hi, (size_t)lo_off, (size_t)(n / 4));
+  CHECK_LAUNCH();
+}
+
+extern "C" int lr2_round_f16(const void* src, void* dst, uint64_t n, void* stream) {
+  if (!src || !dst || n == 0) return LR2_ERR_ARG;
+  if (n % 4) return LR2_ERR_SHAPE;
+  if (misaligned(src, 16) || misaligned(dst, 8)) return LR2_ERR_SHAPE;          // float4 loads, 4 x f16 stores
+  LR2_LAUNCH(round_f16_kernel, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, (const float*)src, (f16_t*)dst,
+             (size_t)(n / 4));
   CHECK_LAUNCH();
 }
 

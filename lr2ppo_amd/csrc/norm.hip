@@ -90,6 +90,63 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
   }
 }
 
+// layernorm_fwd_kernel with the single plane in f16 (the "f16" inference mode: common.h's f16 plane writer): the same statistics and
+// the same fp32 row, written as fp32 and / or ONE f16 plane
+__global__ __launch_bounds__(256) void layernorm_fwd_f16_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                                const float* __restrict__ beta, float* __restrict__ out,
+                                                                f16_t* __restrict__ out_h, float* __restrict__ mean_out,
+                                                                float* __restrict__ rstd_out, int rows, int D, float eps,
+                                                                int mode, int group, uint64_t group_stride) {
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= rows) return;
+  const float* xr = x + (size_t)r * D;
+  float4 v[MAXV];
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < MAXV; ++i) {
+    const int e = (i * 64 + lane) * 4;
+    if (e < D) {
+      v[i] = *reinterpret_cast<const float4*>(xr + e);
+      s += v[i].x + v[i].y + v[i].z + v[i].w;
+    }
+  }
+  const float mean = wave_sum(s) / (float)D;
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < MAXV; ++i) {
+    const int e = (i * 64 + lane) * 4;
+    if (e < D) {
+      const float a = v[i].x - mean, b = v[i].y - mean, c = v[i].z - mean, d = v[i].w - mean;
+      q += a * a + b * b + c * c + d * d;
+    }
+  }
+  q = wave_sum(q);
+  float rstd;
+  if (mode == 0) rstd = 1.0f / sqrtf(q / (float)D + eps);
+  else rstd = 1.0f / (sqrtf(q / (float)(D - 1)) + eps);
+  if (lane == 0) {
+    if (mean_out) mean_out[r] = mean;
+    if (rstd_out) rstd_out[r] = rstd;
+  }
+  const size_t off = mapped_row_offset(r, group, group_stride, D);
+#pragma unroll
+  for (int i = 0; i < MAXV; ++i) {
+    const int e = (i * 64 + lane) * 4;
+    if (e < D) {
+      const float4 g = *reinterpret_cast<const float4*>(gamma + e);
+      const float4 b = *reinterpret_cast<const float4*>(beta + e);
+      float4 y;
+      y.x = (v[i].x - mean) * rstd * g.x + b.x;
+      y.y = (v[i].y - mean) * rstd * g.y + b.y;
+      y.z = (v[i].z - mean) * rstd * g.z + b.z;
+      y.w = (v[i].w - mean) * rstd * g.w + b.w;
+      if (out) *reinterpret_cast<float4*>(out + off + e) = y;
+      if (out_h) store_f16x4(out_h + off + e, y);
+    }
+  }
+}
+
 // dx = rstd * (g - mean(g) - xhat * c2), g = dy*gamma
 //   mode 0 (nn.LayerNorm, biased variance, eps inside the sqrt):      c2 = sum(g*xhat) / D
 //   mode 1 (TencentPretrain LayerNorm, y = gamma (x - mean) / (std + eps) + beta with the UNBIASED std, layer_norm.py:16-21):
@@ -277,6 +334,17 @@ extern "C" int lr2_layernorm_fwd(const void* x, const void* gamma, const void* b
   LR2_LAUNCH(layernorm_fwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const float*)x,
              (const float*)gamma, (const float*)beta, (float*)out, (bf16_t*)out_hi, (size_t)out_lo_off, (float*)mean,
              (float*)rstd, rows, D, eps, mode, group, group_stride, (uint8_t*)nullptr, (uint8_t*)nullptr);
+  return lr2_launch_status(__func__);
+}
+
+extern "C" int lr2_layernorm_fwd_f16(const void* x, const void* gamma, const void* beta, void* out, void* out_f16, void* mean,
+                                     void* rstd, int rows, int D, float eps, int mode, int group, uint64_t group_stride, void* stream) {
+  if (!x || !gamma || !beta || (!out && !out_f16) || rows <= 0) return LR2_ERR_ARG;
+  if (D % 4 != 0 || D > MAXV * 256 || D < 4) return LR2_ERR_SHAPE;
+  if (group <= 0) { group = rows; group_stride = 0; }
+  LR2_LAUNCH(layernorm_fwd_f16_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const float*)x,
+             (const float*)gamma, (const float*)beta, (float*)out, (f16_t*)out_f16, (float*)mean, (float*)rstd, rows, D, eps, mode,
+             group, group_stride);
   return lr2_launch_status(__func__);
 }
 

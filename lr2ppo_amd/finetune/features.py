@@ -158,7 +158,9 @@ class FeatureExtractor(nn.Module):
     (TransformerEncoder._forward_train_fp8 / _backward_train_fp8) on every route, extract() included (that forward, dropout off) --
     or "bf16" (BASELINE.json configs[2]'s literal dtype): extract() / no-grad forward() run every projection and the attention
     of both stacks as ONE bf16 pass over single-plane activations (TransformerEncoder.forward_bf16); inference only, like "mxfp8",
-    ten times closer to the parity path than it -- or "bf16_train": fine-tuning in single-pass bf16, every projection's forward, input
+    ten times closer to the parity path than it -- or "f16": the "bf16" mode with every single plane in IEEE binary16
+    (TransformerEncoder.forward_f16: 11 significand bits per operand instead of 8, the same cost, eight times closer to the parity path;
+    inference only; attention_long is refused: there is no key-blocked f16 kernel) -- or "bf16_train": fine-tuning in single-pass bf16, every projection's forward, input
     gradient and weight gradient ONE bf16 pass with fp32 accumulation, fp32 residual stream and fp32 master weights
     (TransformerEncoder._forward_train_bf16 / _backward_train_bf16) on every route, extract() included.
     bf16_attention ("bf16_train" only): the attention core of both towers on ONE bf16 plane per operand as well, forward and backward
@@ -172,8 +174,8 @@ class FeatureExtractor(nn.Module):
     before that layer's backward (TransformerEncoder.recompute): the same bits, ~1/12 of the activation memory, one more
     forward per step.  Embeddings, the projection and the heads keep their activations."""
 
-    PRECISIONS = ("split_bf16", "mxfp8", "mxfp8_train", "bf16", "bf16_train")
-    INFERENCE_ONLY = ("mxfp8", "bf16")
+    PRECISIONS = ("split_bf16", "mxfp8", "mxfp8_train", "bf16", "bf16_train", "f16")
+    INFERENCE_ONLY = ("mxfp8", "bf16", "f16")
 
     def __init__(self, vit_args: Optional[argparse.Namespace] = None, text_args: Optional[argparse.Namespace] = None,
                  vocab_size: int = ROBERTA_VOCAB, seq_length: int = 196, feat_dim: Optional[int] = None,
@@ -197,6 +199,9 @@ class FeatureExtractor(nn.Module):
             raise ValueError("bf16_attention_long extends bf16_attention to sequences longer than 288: it needs bf16_attention=True")
         if attention_long and precision not in self.INFERENCE_ONLY:
             raise ValueError(f"attention_long is a switch of the inference modes {self.INFERENCE_ONLY}, not of '{precision}'")
+        if attention_long and precision == "f16":
+            raise ValueError("attention_long: precision='f16' has no key-blocked kernel (sequences longer than 288 take the 3-pass "
+                             "attention); it is a switch of 'bf16' and 'mxfp8'")
         self.precision, self.recompute, self.bf16_attention = precision, bool(recompute), bool(bf16_attention)
         self.bf16_attention_long, self.attention_long = bool(bf16_attention_long), bool(attention_long)
         self.image = EncoderStack(self.vit_args, vocab_size)
@@ -252,15 +257,15 @@ class FeatureExtractor(nn.Module):
         return h0.reshape(B, n_img, -1)
 
     def _fast_now(self) -> Optional[str]:
-        """The encoder method this call takes in an inference-only precision ("forward_fp8" for "mxfp8", "forward_bf16" for "bf16"),
-        None on the other precisions; raises when something asks for gradients or dropout."""
+        """The encoder method this call takes in an inference-only precision ("forward_fp8" for "mxfp8", "forward_bf16" for "bf16",
+        "forward_f16" for "f16"), None on the other precisions; raises when something asks for gradients or dropout."""
         if self.precision not in self.INFERENCE_ONLY:
             return None
         if self.training or (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())):
             raise NotImplementedError(f"FeatureExtractor(precision='{self.precision}') is an inference mode (frozen feature "
                                       "extraction: extract(), or eval() under torch.no_grad()); train the encoders in "
                                       "'split_bf16', 'bf16_train' or 'mxfp8_train'")
-        return "forward_fp8" if self.precision == "mxfp8" else "forward_bf16"
+        return {"mxfp8": "forward_fp8", "bf16": "forward_bf16", "f16": "forward_f16"}[self.precision]
 
     def text_features(self, ids: torch.Tensor, seg: Optional[torch.Tensor] = None) -> torch.Tensor:
         """ids [B, T, L] int64 (+ seg [B, T, L]; default all ones) -> text_emb [B, T, L, hidden]."""
@@ -460,6 +465,10 @@ def raw_input_opts(parser):
     parser.add_argument("--bf16_features", action="store_true",
                         help="with --raw_inputs and frozen encoders: every projection and the attention of both stacks as ONE bf16 "
                              "pass (FeatureExtractor(precision='bf16'); features within ~1e-2 of the default ones)")
+    parser.add_argument("--f16_features", action="store_true",
+                        help="with --raw_inputs and frozen encoders: every projection and the attention of both stacks as ONE f16 "
+                             "pass (FeatureExtractor(precision='f16'); the cost of --bf16_features, features within ~1e-3 of the "
+                             "default ones)")
     parser.add_argument("--fp8_finetune", action="store_true",
                         help="with --raw_inputs --finetune_encoders: train both stacks with MX-FP8 products forward and backward "
                              "(FeatureExtractor(precision='mxfp8_train'))")
@@ -508,13 +517,19 @@ def build_extractor(args, num_tasks: int = 1, trainable: bool = False) -> Featur
     if bf16_attention_long and not bf16_attention:
         raise ValueError("--bf16_attention_long is a switch of the single-plane bf16 attention: it needs --bf16_attention")
     attention_long = bool(getattr(args, "features_attention_long", False))
+    f16 = bool(getattr(args, "f16_features", False))
+    if f16 and (bf16 or fp8 or fp8_train or bf16_train or trainable):
+        raise ValueError("--f16_features is for frozen feature extraction in one f16 pass: it excludes --bf16_features, "
+                         "--fp8_features, --finetune_encoders, --fp8_finetune and --bf16_finetune")
+    if f16 and attention_long:
+        raise ValueError("--f16_features excludes --features_attention_long: there is no key-blocked f16 attention kernel")
     if attention_long and not (bf16 or fp8):
         raise ValueError("--features_attention_long is a switch of the inference modes: it needs --bf16_features or --fp8_features")
     recompute = bool(getattr(args, "recompute_activations", False))
     if recompute and not trainable:
         raise ValueError("--recompute_activations is a training-memory switch: it needs --finetune_encoders")
-    precision = "mxfp8" if fp8 else ("bf16" if bf16 else ("mxfp8_train" if fp8_train else
-                                                               ("bf16_train" if bf16_train else "split_bf16")))
+    precision = "mxfp8" if fp8 else ("bf16" if bf16 else ("f16" if f16 else ("mxfp8_train" if fp8_train else
+                                                                            ("bf16_train" if bf16_train else "split_bf16"))))
     fx = FeatureExtractor(encoder_args(IMAGE_TOWERS.get(tower, tower), **over), encoder_args(TEXT_CONFIG, **over),
                           seq_length=args.seq_length, feat_dim=args.visual_feat_dim, precision=precision,
                           recompute=recompute, bf16_attention=bf16_attention, bf16_attention_long=bf16_attention_long,

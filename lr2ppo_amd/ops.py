@@ -530,6 +530,101 @@ def gemm_bf16_launch_counts():
     return int(c[0]), int(c[1])
 
 
+# ---- the single-pass f16 inference mode (FeatureExtractor(precision="f16")): the bf16 mode's ops with every single plane in f16 ------
+def gemm_f16(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor], M: int, N: int, K: int, *,
+             lda: Optional[int] = None, ldb: Optional[int] = None, ld_out: Optional[int] = None, bias: Optional[torch.Tensor] = None,
+             act: int = 0, resid: Optional[torch.Tensor] = None, alpha: float = 1.0, out_plane: Optional[torch.Tensor] = None,
+             out_planes: Optional[Planes] = None, planes_col: int = 0):
+    """out[M, N] = a[M, K] @ b[N, K]^T (+ bias) (act 1: GELU) (+ resid) as ONE f16 pass (lr2_gemm_f16): a, b are single f16 planes
+    (2-byte HIP tensors: what round_f16, layernorm_fwd_f16, self_attn_fwd_f16 and this product write).  The result goes to `out`
+    (fp32) and / or ONE f16 plane `out_plane` (clamped to +-65504, round to nearest even) or bf16 hi / lo `out_planes` (the operands of
+    the 3-pass attention kernels).  Inference only: the f16 mode, never the parity path.  The 256 x 256 kernel at every size.
+    planes_col: as gemm_bf16."""
+    _chk_f32(out, bias, resid)
+    lda = K if lda is None else lda
+    ldb = K if ldb is None else ldb
+    a_ptr = _plane_ptr(a, (M - 1) * lda + K, "gemm_f16: a")
+    b_ptr = _plane_ptr(b, (N - 1) * ldb + K, "gemm_f16: b")
+    if out_plane is not None and out_planes is not None:
+        raise ValueError("gemm_f16: out_plane excludes out_planes")
+    e = _nat.Epilogue()
+    e.bias, e.resid, e.out = _ptr(bias), _ptr(resid), _ptr(out)
+    e.ld_resid, e.ld_out = _ld(resid, N), (N if ld_out is None else ld_out)
+    if out_plane is not None:
+        e.out_hi, e.out_lo_off, e.ld_planes = _plane_ptr(out_plane, M * N, "gemm_f16: out_plane"), 0, N
+    elif out_planes is not None:
+        if out_planes.rows != M or planes_col < 0 or planes_col % 4 or planes_col + N > out_planes.cols:
+            raise ValueError("gemm_f16: out_planes must be [M, >= planes_col + N], planes_col a multiple of 4")
+        e.out_hi, e.out_lo_off, e.ld_planes = out_planes.data_ptr() + 2 * planes_col, out_planes.lo_off, out_planes.cols
+    e.act, e.alpha = act, alpha
+    with _Timed(f"gemm_f16_M{M}_N{N}_K{K}", 2.0 * M * N * K, 2.0 * (M * K + N * K) + (4.0 if out is not None else 2.0) * M * N):
+        rc = _nat.lib().lr2_gemm_f16(a_ptr, b_ptr, M, N, K, lda, ldb, a.numel() * 2, b.numel() * 2, C.byref(e), _stream())
+    if rc:
+        _nat.check(rc, f"lr2_gemm_f16(M={M},N={N},K={K})")
+    return out if out is not None else (out_plane if out_plane is not None else out_planes)
+
+
+def gemm_f16_launch_count() -> int:
+    """Accepted lr2_gemm_f16 calls since the library was loaded."""
+    c = C.c_uint64(0)
+    _nat.check(_nat.lib().lr2_gemm_f16_launch_count(C.byref(c)), "lr2_gemm_f16_launch_count")
+    return int(c.value)
+
+
+def layernorm_fwd_f16(x, gamma, beta, rows, D, eps, mode, *, group=0, group_stride=0, out=None, mean=None, rstd=None,
+                      out_plane: Optional[torch.Tensor] = None):
+    """layernorm_fwd with the single plane in f16 (lr2_layernorm_fwd_f16): LN(x) to `out` (fp32) and / or ONE f16 plane `out_plane` (a
+    2-byte HIP tensor of rows * D elements: the A operand of gemm_f16); the (group, group_stride) row mapping as layernorm_fwd."""
+    _chk_f32(x, gamma, beta, out, mean, rstd)
+    if out is None and out_plane is None:
+        raise ValueError("layernorm_fwd_f16: out and / or out_plane")
+    hp = _plane_ptr(out_plane, rows * D, "layernorm_fwd_f16: out_plane") if out_plane is not None else None
+    with _Timed(f"lnfwd_f16_R{rows}_D{D}", 0.0, (6.0 if out is None else 10.0 if out_plane is not None else 8.0) * rows * D):
+        rc = _nat.lib().lr2_layernorm_fwd_f16(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(out), hp, _ptr(mean), _ptr(rstd),
+                                              rows, D, eps, mode, group, group_stride, _stream())
+    _nat.check(rc, "lr2_layernorm_fwd_f16")
+    return out if out is not None else out_plane
+
+
+def round_f16(src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
+    """dst = f16(src): an fp32 HIP tensor -> ONE f16 plane (a 2-byte HIP tensor of at least src.numel() elements) by the mode's plane
+    writer (clamp to +-65504, round to nearest even; lr2_round_f16)."""
+    _chk_f32(src)
+    n = src.numel()
+    with _Timed(f"round_f16_{n}", 0.0, 6.0 * n):
+        rc = _nat.lib().lr2_round_f16(src.data_ptr(), _plane_ptr(dst, n, "round_f16: dst"), n, _stream())
+    _nat.check(rc, "lr2_round_f16")
+    return dst
+
+
+def self_attn_fwd_f16(qkv: torch.Tensor, seg, *, batch, heads, L, head_dim, scale, out: Optional[torch.Tensor] = None,
+                      out_plane: Optional[torch.Tensor] = None):
+    """Encoder self-attention of the f16 mode (lr2_self_attn_fwd_f16).  qkv: ONE f16 plane [batch * L, 3E] = [Q | K | V] (a 2-byte HIP
+    tensor: what gemm_f16(out_plane=...) writes); the context as fp32 `out` [batch * L, E] and / or as ONE f16 plane `out_plane` (a
+    2-byte HIP tensor [batch * L, E])."""
+    E = heads * head_dim
+    if qkv.element_size() != 2 or not qkv.is_cuda or qkv.numel() < batch * L * 3 * E:
+        raise TypeError("self_attn_fwd_f16: qkv is a 2-byte HIP tensor [batch * L, 3 * heads * head_dim]")
+    if seg.dtype != torch.int64:
+        raise TypeError("seg must be int64")
+    _chk_f32(out)
+    if out is None and out_plane is None:
+        raise ValueError("self_attn_fwd_f16: out and / or out_plane")
+    ob = _plane_ptr(out_plane, batch * L * E, "self_attn_fwd_f16: out_plane") if out_plane is not None else None
+    base = qkv.data_ptr()
+    with _Timed(f"selfattn_f16_B{batch}_H{heads}_L{L}", 4.0 * batch * heads * L * L * head_dim, 7.0 * batch * L * E):
+        _nat.check(_nat.lib().lr2_self_attn_fwd_f16(base, base + 2 * E, base + 4 * E, 3 * E, seg.data_ptr(), _ptr(out), ob, E, batch,
+                                                    heads, L, head_dim, scale, _stream()), "lr2_self_attn_fwd_f16")
+    return out if out is not None else out_plane
+
+
+def self_attn_fwd_f16_launch_count() -> int:
+    """Accepted lr2_self_attn_fwd_f16 calls since the library was loaded."""
+    c = C.c_uint64(0)
+    _nat.check(_nat.lib().lr2_self_attn_fwd_f16_launch_count(C.byref(c)), "lr2_self_attn_fwd_f16_launch_count")
+    return int(c.value)
+
+
 # ---- single-pass bf16 products of encoder training (the "bf16_train" mode, DESIGN 4.6) --------------------------------------------
 _BF16_TRAIN_FORCE_256 = False
 

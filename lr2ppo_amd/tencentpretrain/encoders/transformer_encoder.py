@@ -472,6 +472,111 @@ class TransformerEncoder(nn.Module):
             out.view(M, E).copy_(h)
         return out
 
+    # ---- single-pass f16 inference: forward_bf16's schedule with every single plane in IEEE binary16 (11 significand bits per operand
+    # instead of 8: DESIGN 2).  NOT the parity path.  Same sites replaced as forward_bf16.
+    def _f16_weights(self):
+        """Per layer: the four projection weights as ONE f16 plane each (ops.round_f16 of the fp32 parameters -- not the bf16 hi planes
+        of _weight_planes), rounded once and again when a parameter is rewritten (_fp8_weights' signature)."""
+        sig = tuple((p.data_ptr(), p._version, ops.param_write_count(p)) for p in self.parameters())
+        if getattr(self, "_f16_sig", None) != sig:
+            def plane(t):
+                return ops.round_f16(t.contiguous(), torch.empty(t.numel(), dtype=torch.float16, device=t.device))
+            out = []
+            for layer in self.transformer:
+                att, ffn = layer.self_attn, layer.feed_forward
+                out.append({"wqkv": plane(torch.cat([l.weight.data for l in att.linear_layers], 0)),      # rows Q | K | V
+                            "bqkv": torch.cat([l.bias.data for l in att.linear_layers], 0),
+                            "wo": plane(att.final_linear.weight.data), "w1": plane(ffn.linear_1.weight.data),
+                            "w2": plane(ffn.linear_2.weight.data)})
+            self._f16_w, self._f16_sig = out, sig
+        return self._f16_w
+
+    @torch.no_grad()
+    def forward_f16(self, emb, seg, first_only: bool = False):
+        """forward(emb, seg) with every GEMM operand ONE f16 plane and every projection ONE f16 pass (ops.gemm_f16,
+        csrc/gemm256_f16.hip): forward_bf16's schedule -- the LayerNorm output (ops.layernorm_fwd_f16), Q | K | V as one [M, 3E] plane, the
+        attention context (ops.self_attn_fwd_f16) and GELU(z) are written as a single f16 plane each by the kernel that produces them; the
+        residual stream stays fp32.  The weights are f16 planes of the fp32 parameters (_f16_weights).  The bf16 mode's cost with eight
+        times less operand rounding -- FeatureExtractor(precision="f16").
+        L > 288: the 3-pass attention kernels (the QKV product then writes bf16 hi / lo planes, the context goes through ops.round_f16);
+        there is no key-blocked f16 kernel.  Head width below 64 (a multiple of 4): forward_bf16's zero-padded heads on the same kernels.
+        first_only: -> hidden[:, 0, :] ([batch, hidden]): the last layer computes K | V for every row (an f16 product into hi / lo planes)
+        and everything behind the scores for row 0 only (forward_first_token's schedule, B rows: split-bf16)."""
+        if emb.dtype != torch.float32 or not emb.is_cuda:
+            raise TypeError("lr2ppo_amd: emb must be a float32 tensor on the HIP device (no CPU path)")
+        B, L, E = emb.shape
+        H, hd, M = self.heads_num, E // self.heads_num, B * L
+        F = self.transformer[0].feed_forward.linear_1.out_features
+        if E % 64 or F % 64:
+            raise ValueError("forward_f16: hidden and feed-forward widths must be multiples of 64")
+        if hd != 64 and (hd > 64 or hd % 4):
+            raise ValueError("forward_f16: head width must be 64, or a multiple of 4 below it (zero-padded heads)")
+        if first_only and hd != 64:                                   # lr2_first_token_attn is built for head width 64
+            return self.forward_f16(emb, seg)[:, 0, :].contiguous()
+        if self._ws is None or self._ws.device != emb.device:
+            self._ws = engine.Workspace(emb.device)
+        ws, dev = self._ws, emb.device
+        seg = seg.to(device=dev, dtype=torch.int64).contiguous().view(-1)
+        W = self._f16_weights()
+        pre = self.layernorm_positioning == "pre"
+        h, h2 = ws.mat("h", M, E), ws.mat("h2", M, E)
+        # the planes buffers of _forward_infer, their first half used as the single f16 plane
+        qkv_p = ws.planes("qkv_p", M, 3 * E)
+        x_b, qkv_b, o_b = ws.planes("x_p", M, E).buf[:M * E], qkv_p.buf[:M * 3 * E], ws.planes("o_p", M, E).buf[:M * E]
+        t_b, ff_b = ws.planes("t_p", M, E).buf[:M * E], ws.planes("ff_p", M, F).buf[:M * F]
+        fast_attn = hd == 64 and L <= 288
+        h.copy_(emb.contiguous().view(M, E))
+        scale = 1.0 / math.sqrt(float(hd))
+        if not pre:
+            ops.round_f16(h, x_b)                                     # the first layer's operand
+        for li, (layer, w) in enumerate(zip(self.transformer, W)):
+            att, ffn, ln1, ln2 = layer.self_attn, layer.feed_forward, layer.layer_norm_1, layer.layer_norm_2
+            if pre:
+                ops.layernorm_fwd_f16(h, ln1.gamma.data, ln1.beta.data, rows=M, D=E, eps=ln1.eps, mode=1, out_plane=x_b)
+            if first_only and li == self.layers_num - 1:
+                kv_p = ws.planes("kv_p", M, 2 * E)
+                ops.gemm_f16(x_b, w["wqkv"][E * E:], None, M, 2 * E, E, bias=w["bqkv"][E:], out_planes=kv_p)
+                return self._last_layer_first_token(ws, layer, self._weight_planes(dev)[li], h, None, seg, B, L, E, F, kv_p=kv_p)
+            if fast_attn:
+                ops.gemm_f16(x_b, w["wqkv"], None, M, 3 * E, E, bias=w["bqkv"], out_plane=qkv_b)
+                ops.self_attn_fwd_f16(qkv_b, seg, batch=B, heads=H, L=L, head_dim=hd, scale=scale, out_plane=o_b)
+            elif hd != 64:
+                Ep, o32 = H * 64, ws.mat("bf16_o", M, E)
+                pad_p, pad_o = ws.planes("bf16_qkv_pad", M, 3 * Ep), ws.mat("bf16_o_pad", M, Ep)
+                if li == 0:
+                    pad_p.buf[:2 * M * 3 * Ep].zero_()                 # the padding columns: written by nothing below
+                for blk in range(3):
+                    for hh in range(H):
+                        r0 = blk * E + hh * hd                        # rows of [Wq; Wk; Wv] = this head's output columns
+                        ops.gemm_f16(x_b, w["wqkv"][r0 * E:(r0 + hd) * E], None, M, hd, E, bias=w["bqkv"][r0:r0 + hd],
+                                     out_planes=pad_p, planes_col=blk * Ep + hh * 64)
+                ops.self_attn_fwd(pad_p, seg, pad_o, batch=B, heads=H, L=L, head_dim=64, scale=scale)
+                o32.copy_(pad_o.view(M, H, 64)[:, :, :hd].reshape(M, E))
+                ops.round_f16(o32, o_b)
+            else:
+                o32 = ws.mat("bf16_o", M, E)
+                ops.gemm_f16(x_b, w["wqkv"], None, M, 3 * E, E, bias=w["bqkv"], out_planes=qkv_p)     # the 3-pass kernels take hi / lo planes
+                ops.self_attn_fwd(qkv_p, seg, o32, batch=B, heads=H, L=L, head_dim=hd, scale=scale)
+                ops.round_f16(o32, o_b)
+            ops.gemm_f16(o_b, w["wo"], h2, M, E, E, bias=att.final_linear.bias.data, resid=h)
+            if pre:                                                   # layers/transformer.py:63-73
+                ops.layernorm_fwd_f16(h2, ln2.gamma.data, ln2.beta.data, rows=M, D=E, eps=ln2.eps, mode=1, out_plane=t_b)
+                ops.gemm_f16(t_b, w["w1"], None, M, F, E, bias=ffn.linear_1.bias.data, act=1, out_plane=ff_b)
+                ops.gemm_f16(ff_b, w["w2"], h, M, E, F, bias=ffn.linear_2.bias.data, resid=h2)
+            else:                                                     # layers/transformer.py:54-61
+                xn = ws.mat("bf16_xn", M, E)
+                ops.layernorm_fwd_f16(h2, ln1.gamma.data, ln1.beta.data, rows=M, D=E, eps=ln1.eps, mode=1, out=xn, out_plane=t_b)
+                ops.gemm_f16(t_b, w["w1"], None, M, F, E, bias=ffn.linear_1.bias.data, act=1, out_plane=ff_b)
+                ops.gemm_f16(ff_b, w["w2"], h2, M, E, F, bias=ffn.linear_2.bias.data, resid=xn)
+                ops.layernorm_fwd_f16(h2, ln2.gamma.data, ln2.beta.data, rows=M, D=E, eps=ln2.eps, mode=1, out=h, out_plane=x_b)
+        out = torch.empty(B, L, E, device=dev)
+        if self.final_layernorm:
+            ops.layernorm_fwd(h, self.layer_norm.gamma.data, self.layer_norm.beta.data, out.view(M, E), rows=M, D=E,
+                              eps=self.layer_norm.eps, mode=1)
+        else:
+            out.view(M, E).copy_(h)
+        return out
+
     def _last_layer_first_token(self, ws, layer, w, h, x_p, seg, B, L, E, F, kv_p=None):
         """Last layer of the inference schedule for row 0 of every sequence.  h: the layer's input [B*L, E] (fp32); x_p: the
         planes its QKV projection reads (LayerNorm_1(h) for 'pre', h itself for 'post').  K, V: all rows; everything after the

@@ -42,5 +42,8 @@ python -m lr2ppo_amd.finetune.reward_pair_dataloader $COMMON --mode cls --epochs
 python -m lr2ppo_amd.finetune.ppo $COMMON --mode reg --epochs_num 2 --critic_learning_rate 1e-4 --max_timesteps 1 \
   --update_timesteps 2 --kl_div_loss_weight 0.001 --entropy_weight 0.001 --value_clip 0.5 --max_cycles 1 $RAW \
   --output_model_path "$OUT/stage3_bf16.bin" --log_path "$OUT/stage3_bf16.log"
+echo "== ... and in ONE f16 pass (--f16_features): stage 2"
+python -m lr2ppo_amd.finetune.reward_pair_dataloader $COMMON --mode cls --epochs_num 1 --report_steps 2 --max_steps 2 \
+  ${RAW/--bf16_features/--f16_features} --output_model_path "$OUT/stage2_f16.bin" --log_path "$OUT/stage2_f16.log"
 ls -la "$OUT"
 echo CLI_SMOKE_OK

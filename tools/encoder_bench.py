@@ -3,7 +3,8 @@ Prints ms per forward, algorithmic TFLOP/s (2MNK of the GEMMs + 4 L^2 d of atten
 from HIP events.  python tools/encoder_bench.py [--batch 32] [--iters 10] [--passes 3]
 --train [--precision mxfp8_train | bf16_train [--bf16-attention [--bf16-attention-long]]] [--recompute]: forward + backward per step, and
 the step's peak device memory.  --text-seq L / --only text | image: the text tower at another sequence length / one tower alone.
---ppo-shapes --precision bf16 | mxfp8 with --text-seq / --only: the per-tower loop on that inference schedule (forward_bf16 / forward_fp8);
+--ppo-shapes --precision bf16 | f16 | mxfp8 with --text-seq / --only: the per-tower loop on that inference schedule (forward_bf16 /
+forward_f16 / forward_fp8);
 [--attention-long]: sequences longer than 288 on the key-blocked single-plane attention (TransformerEncoder.infer_attention_long)."""
 import argparse
 import os
@@ -47,7 +48,8 @@ def measure_forward(batch_items=32, tags=2, n_img=16, iters=3, passes=3, dev=Non
     """Dual-encoder forward at the PPO step's feature-extraction shapes: ViT-B/16 over batch_items*n_img frames
     [*, 197, 768], RoBERTa-base over batch_items*tags label sequences [*, 196, 768]; random N(0, 0.02) weights.
     -> {"ms", "algorithmic_tflop", "tflops", "mfma_issue_frac"} (MFMA issue fraction = passes * flops / time / 2.5 PF).
-    precision: "split_bf16" (enc.forward), "bf16" (enc.forward_bf16: one pass) or "mxfp8" (enc.forward_fp8)."""
+    precision: "split_bf16" (enc.forward), "bf16" (enc.forward_bf16: one pass), "f16" (enc.forward_f16: one pass) or "mxfp8"
+    (enc.forward_fp8)."""
     dev = dev or torch.device("cuda:0")
     ops.set_gemm_passes(passes)
     if precision != "split_bf16":
@@ -62,7 +64,7 @@ def measure_forward(batch_items=32, tags=2, n_img=16, iters=3, passes=3, dev=Non
         enc = enc.to(dev).eval()
         emb = torch.randn(B, L, 768, device=dev)
         seg = torch.ones(B, L, dtype=torch.int64, device=dev)
-        fwd = {"split_bf16": enc, "bf16": enc.forward_bf16, "mxfp8": enc.forward_fp8}[precision]
+        fwd = {"split_bf16": enc, "bf16": enc.forward_bf16, "f16": enc.forward_f16, "mxfp8": enc.forward_fp8}[precision]
         with torch.no_grad():
             fwd(emb, seg)
             torch.cuda.synchronize()
@@ -93,9 +95,9 @@ def parse_args(argv=None):
     ap.add_argument("--detail", action="store_true", help="per-signature launch averages")
     ap.add_argument("--train", action="store_true", help="time forward + backward (train mode, dropout 0.1) instead; with "
                     "--ppo-shapes: both towers at the PPO sizes (ViT over batch*16 frames, RoBERTa over batch*2 sequences)")
-    ap.add_argument("--precision", choices=("split_bf16", "mxfp8_train", "bf16_train", "bf16", "mxfp8"), default="split_bf16",
+    ap.add_argument("--precision", choices=("split_bf16", "mxfp8_train", "bf16_train", "bf16", "f16", "mxfp8"), default="split_bf16",
                     help="--train: the encoders' training precision (split_bf16 | mxfp8_train | bf16_train); "
-                         "--ppo-shapes without --train: the inference precision (split_bf16 | bf16 | mxfp8)")
+                         "--ppo-shapes without --train: the inference precision (split_bf16 | bf16 | f16 | mxfp8)")
     ap.add_argument("--recompute", action="store_true",
                     help="--train: keep each layer's input only and re-run a layer's forward in front of its backward "
                          "(TransformerEncoder.recompute); the peak-memory figure shows what that buys, the step time what it costs")
@@ -117,17 +119,17 @@ def parse_args(argv=None):
         ap.error("--text-seq: 1 .. %d" % ROBERTA["max_seq_length"])
     if a.attention_long and (a.train or a.precision not in ("bf16", "mxfp8")):
         ap.error("--attention-long is a switch of the inference modes: give --precision bf16 | mxfp8, not --train")
-    if (a.text_seq != 196 or a.only != "both") and a.ppo_shapes and not a.train and a.precision not in ("bf16", "mxfp8"):
+    if (a.text_seq != 196 or a.only != "both") and a.ppo_shapes and not a.train and a.precision not in ("bf16", "f16", "mxfp8"):
         ap.error("--text-seq / --only are switches of the per-tower loop: not of --ppo-shapes without --train "
-                 "(--precision bf16 | mxfp8 excepted: they then run the per-tower loop on their own schedule)")
+                 "(--precision bf16 | f16 | mxfp8 excepted: they then run the per-tower loop on their own schedule)")
     if a.bf16_attention and not (a.train and a.precision == "bf16_train"):
         ap.error("--bf16-attention is a switch of --train --precision bf16_train")
     if a.recompute and not a.train:
         ap.error("--recompute is a switch of the training schedule: give --train")
     if a.precision == "bf16_train" and not a.train:
         ap.error("--precision bf16_train is a training precision: give --train")
-    if a.precision in ("bf16", "mxfp8") and (a.train or not a.ppo_shapes):
-        ap.error("--precision bf16 / mxfp8 are inference modes: give --ppo-shapes, not --train")
+    if a.precision in ("bf16", "f16", "mxfp8") and (a.train or not a.ppo_shapes):
+        ap.error("--precision bf16 / f16 / mxfp8 are inference modes: give --ppo-shapes, not --train")
     return a
 
 
@@ -136,7 +138,7 @@ def main():
     dev = torch.device("cuda:0")
     ops.set_gemm_passes(a.passes)
     torch.manual_seed(0)
-    infer = a.precision if a.precision in ("bf16", "mxfp8") else None          # (parse_args: never with --train)
+    infer = a.precision if a.precision in ("bf16", "f16", "mxfp8") else None          # (parse_args: never with --train)
     per_tower = infer is not None and (a.text_seq != 196 or a.only != "both" or a.attention_long)
     if a.ppo_shapes and not a.train and not per_tower:
         prec = "split_bf16" if a.precision == "mxfp8_train" else a.precision      # (a training precision: ignored without --train)
@@ -160,7 +162,7 @@ def main():
         enc.bf16_attention_long = a.bf16_attention_long
         enc.recompute = a.recompute
         enc.infer_attention_long = a.attention_long
-        infer_fwd = {"bf16": enc.forward_bf16, "mxfp8": enc.forward_fp8, None: enc}[infer]
+        infer_fwd = {"bf16": enc.forward_bf16, "f16": enc.forward_f16, "mxfp8": enc.forward_fp8, None: enc}[infer]
         B = (a.batch * 16 if name.startswith("vit") else a.batch * 2) if a.ppo_shapes else a.batch
         emb = torch.randn(B, L, 768, device=dev, requires_grad=a.train)
         seg = torch.ones(B, L, dtype=torch.int64, device=dev)

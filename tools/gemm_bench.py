@@ -2,6 +2,7 @@
 """Micro-benchmark of lr2_gemm on the shapes of the LR2PPO head (run on the GPU box).
 usage: python tools/gemm_bench.py [--passes 3] [--iters 20]
        python tools/gemm_bench.py --bf16 [--bm 256|128] [--only ...]: the single-pass bf16 product (lr2_gemm_bf16) on the NT shapes
+       python tools/gemm_bench.py --f16 [--only ...]: the single-pass f16 product (lr2_gemm_f16: the 256 x 256 kernel at every size)
        python tools/gemm_bench.py --bf16 --tn [--bm 256|128] [--splits S] [--only ...]: the single-pass weight gradient
            (lr2_gemm_bf16_train, TN) on TN_B1_SHAPES, bias gradient included; without --bm each shape is timed on the 256 x 256 TN
            kernel, on the 128-row family at passes = 1 and on the 3-pass 256 x 256 TN kernel, in that order"""
@@ -97,8 +98,12 @@ def main():
     ap.add_argument("--splits", type=int, default=None, help="override split-K factor")
     ap.add_argument("--bf16", action="store_true", help="ONE bf16 plane per operand, one pass (ops.gemm_bf16; NT shapes only); "
                     "--bm 256: the 256 x 256 single-pass kernel, --bm 128: the 128-row family at passes = 1; default: by size")
+    ap.add_argument("--f16", action="store_true", help="ONE f16 plane per operand, one pass (ops.gemm_f16; NT shapes only): the "
+                    "256 x 256 kernel at every size (--bm is ignored)")
     ap.add_argument("--tn", action="store_true", help="with --bf16: the single-pass weight gradient (ops.gemm_bf16_train, TN) on TN_B1_SHAPES")
     a = ap.parse_args()
+    if a.f16 and (a.bf16 or a.tn):
+        ap.error("--f16 is a mode of its own: it excludes --bf16 and --tn")
     if a.tn and not a.bf16:
         ap.error("--tn is the weight-gradient form of the single-pass product: give --bf16")
     dev = torch.device("cuda:0")
@@ -109,6 +114,16 @@ def main():
         if a.only is not None and si not in a.only:
             continue
         ta, tb = form == "TN", form in ("NN", "TN")
+        if a.f16:
+            if form != "NT" or K % 64:
+                continue
+            A = torch.randn(M, K, device=dev, generator=g).to(torch.float16)
+            B = torch.randn(N, K, device=dev, generator=g).to(torch.float16)
+            out = torch.empty(M, N, device=dev)
+            ms = _time(lambda: ops.gemm_f16(A, B, out, M, N, K), a.iters)
+            print(f"f16x1 NT M={M:6d} N={N:6d} K={K:6d} bm=256: {ms:8.4f} ms  {2.0 * M * N * K / ms / 1e9:7.1f} TFLOP/s", flush=True)
+            del A, B, out
+            continue
         if a.bf16:
             if form != "NT" or K % 64:
                 continue
