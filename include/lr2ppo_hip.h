@@ -590,6 +590,28 @@ int lr2_self_attn_fwd_f16(const void* q, const void* k, const void* v, int ld, c
 /* Diagnostic: *count = accepted lr2_self_attn_fwd_f16 calls since the library was loaded.
  * replaces: nothing (a test hook, as lr2_self_attn_fwd_bf16_blocked_launch_count: which attention a schedule ran). */
 int lr2_self_attn_fwd_f16_launch_count(uint64_t* count);
+/* Added within ABI 27 (purely additive: no signature or struct changes).  lr2_self_attn_fwd_f16 for sequences longer than one
+ * LDS-resident head (FeatureExtractor(precision="f16", f16_attention_long=True); csrc/selfattn_f16_blocked.hip): that call's
+ * argument list, layout, key mask and two outputs -- q / k / v ONE f16 plane each (row stride ld), the context rows out as fp32 (o_f32
+ * [batch * L, ld_o]) and / or as ONE f16 plane (o_f16 [batch * L, ld_o]: clamp to +-65504, round to nearest even of the fp32 context);
+ * any non-empty subset -- with the keys walked in blocks through LDS by lr2_self_attn_fwd_bf16_blocked's loop on the f16 MFMA:
+ * lr2_self_attn_bf16_blocked_plan's fwd_key_block keys per block, per 16-query sub-tile a running maximum m, the fp32 sum l of the
+ * unrounded p~ = exp2(s - m) and the un-normalised accumulator, both rescaled by exp2(m - m') when m grows; p~ (in (0, 1]) rounded to
+ * f16 (nearest even, subnormals kept) as the A operand of P V; context = accumulator / l.  No dropout, no lse, no MX-FP8 outputs.
+ * head_dim 64, any L >= 1 (so 1 <= L <= 288 can be run in both forms), one workgroup of 8 waves per (sequence, head, chunk of 512
+ * queries).  Inference only.  NOT the parity path: lr2_self_attn_fwd stays the default, and lr2_self_attn_fwd_f16 is unchanged (it still
+ * answers LR2_ERR_SHAPE at L = 289).
+ * LR2_ERR_ARG: a NULL q / k / v / seg; no output at all; q / k / v / o_f32 not 16-byte or o_f16 not 8-byte aligned; batch or heads <= 0.
+ * LR2_ERR_SHAPE: head_dim != 64; L < 1; ld % 8; ld_o % 4; ld or ld_o below heads * 64.  Nothing is launched (and nothing counted) by a
+ * rejected call.
+ * replaces: tencentpretrain/layers/multi_headed_attn.py:60-74 in that mode at the sequence lengths lr2_self_attn_fwd_f16 does not
+ * serve. */
+int lr2_self_attn_fwd_f16_blocked(const void* q, const void* k, const void* v, int ld, const int64_t* seg, void* o_f32, void* o_f16,
+                                  int ld_o, int batch, int heads, int L, int head_dim, float scale, void* stream);
+/* Diagnostic (added within ABI 27): *count = accepted lr2_self_attn_fwd_f16_blocked calls since the library was loaded (a plain host
+ * counter, not synchronised).  LR2_ERR_ARG for a NULL count.
+ * replaces: nothing (a test hook, as lr2_self_attn_fwd_f16_launch_count: which attention a schedule ran). */
+int lr2_self_attn_fwd_f16_blocked_launch_count(uint64_t* count);
 
 /* ABI 20.  MX-FP8 encoder training (FeatureExtractor(precision="mxfp8_train")): the backward's operands, blocked along the axis its
  * products reduce over, and a K-sliced weight-gradient product.

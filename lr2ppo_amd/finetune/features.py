@@ -160,7 +160,7 @@ class FeatureExtractor(nn.Module):
     of both stacks as ONE bf16 pass over single-plane activations (TransformerEncoder.forward_bf16); inference only, like "mxfp8",
     ten times closer to the parity path than it -- or "f16": the "bf16" mode with every single plane in IEEE binary16
     (TransformerEncoder.forward_f16: 11 significand bits per operand instead of 8, the same cost, eight times closer to the parity path;
-    inference only; attention_long is refused: there is no key-blocked f16 kernel) -- or "bf16_train": fine-tuning in single-pass bf16, every projection's forward, input
+    inference only; attention_long is refused: the key-blocked f16 kernel has a switch of its own, f16_attention_long) -- or "bf16_train": fine-tuning in single-pass bf16, every projection's forward, input
     gradient and weight gradient ONE bf16 pass with fp32 accumulation, fp32 residual stream and fp32 master weights
     (TransformerEncoder._forward_train_bf16 / _backward_train_bf16) on every route, extract() included.
     bf16_attention ("bf16_train" only): the attention core of both towers on ONE bf16 plane per operand as well, forward and backward
@@ -170,6 +170,9 @@ class FeatureExtractor(nn.Module):
     attention_long ("bf16" and "mxfp8" only): the two inference modes run sequences longer than 288 (head_dim 64) on ONE bf16 plane per
     operand too, on the key-blocked kernel of csrc/selfattn_mx_blocked.hip instead of the 3-pass attention
     (TransformerEncoder.infer_attention_long); sequences up to 288 are unaffected.
+    f16_attention_long ("f16" only): that mode runs sequences longer than 288 (head_dim 64) on ONE f16 plane per operand too, on the
+    key-blocked kernel of csrc/selfattn_f16_blocked.hip instead of the 3-pass attention (TransformerEncoder.f16_attention_long,
+    DESIGN 4.5); sequences up to 288 are unaffected.
     recompute: the training forwards of both towers keep each layer's input only and the backward re-runs a layer's forward right
     before that layer's backward (TransformerEncoder.recompute): the same bits, ~1/12 of the activation memory, one more
     forward per step.  Embeddings, the projection and the heads keep their activations."""
@@ -180,7 +183,7 @@ class FeatureExtractor(nn.Module):
     def __init__(self, vit_args: Optional[argparse.Namespace] = None, text_args: Optional[argparse.Namespace] = None,
                  vocab_size: int = ROBERTA_VOCAB, seq_length: int = 196, feat_dim: Optional[int] = None,
                  precision: str = "split_bf16", recompute: bool = False, bf16_attention: bool = False,
-                 bf16_attention_long: bool = False, attention_long: bool = False):
+                 bf16_attention_long: bool = False, attention_long: bool = False, f16_attention_long: bool = False):
         super().__init__()
         self.vit_args = vit_args or encoder_args(VIT_CONFIG)
         self.text_args = text_args or encoder_args(TEXT_CONFIG)
@@ -200,10 +203,13 @@ class FeatureExtractor(nn.Module):
         if attention_long and precision not in self.INFERENCE_ONLY:
             raise ValueError(f"attention_long is a switch of the inference modes {self.INFERENCE_ONLY}, not of '{precision}'")
         if attention_long and precision == "f16":
-            raise ValueError("attention_long: precision='f16' has no key-blocked kernel (sequences longer than 288 take the 3-pass "
-                             "attention); it is a switch of 'bf16' and 'mxfp8'")
+            raise ValueError("attention_long is a switch of 'bf16' and 'mxfp8' (the key-blocked bf16 kernel); precision='f16' reaches "
+                             "its own key-blocked kernel with f16_attention_long=True")
+        if f16_attention_long and precision != "f16":
+            raise ValueError(f"f16_attention_long is a switch of precision='f16', not of '{precision}'")
         self.precision, self.recompute, self.bf16_attention = precision, bool(recompute), bool(bf16_attention)
         self.bf16_attention_long, self.attention_long = bool(bf16_attention_long), bool(attention_long)
+        self.f16_attention_long = bool(f16_attention_long)
         self.image = EncoderStack(self.vit_args, vocab_size)
         self.text = EncoderStack(self.text_args, vocab_size)
         self.visual_projection = (VisualProjection(self.vit_args.hidden_size, self.feat_dim)
@@ -215,6 +221,7 @@ class FeatureExtractor(nn.Module):
         self.image.encoder.bf16_attention = self.text.encoder.bf16_attention = self.bf16_attention
         self.image.encoder.bf16_attention_long = self.text.encoder.bf16_attention_long = self.bf16_attention_long
         self.image.encoder.infer_attention_long = self.text.encoder.infer_attention_long = self.attention_long
+        self.image.encoder.f16_attention_long = self.text.encoder.f16_attention_long = self.f16_attention_long
 
     def saved_activation_bytes(self, frames_shape, ids_shape) -> int:
         """Bytes of encoder activations forward_train keeps until backward_train for frames [B, n_img, ...] and ids [B, T, L]: the
@@ -484,6 +491,9 @@ def raw_input_opts(parser):
     parser.add_argument("--features_attention_long", action="store_true",
                         help="with --bf16_features or --fp8_features: sequences longer than 288 on ONE bf16 plane per operand too, on "
                              "the key-blocked kernel (FeatureExtractor(precision='bf16' | 'mxfp8', attention_long=True); head_dim 64)")
+    parser.add_argument("--f16_attention_long", action="store_true",
+                        help="with --f16_features: sequences longer than 288 on ONE f16 plane per operand too, on the key-blocked "
+                             "f16 kernel (FeatureExtractor(precision='f16', f16_attention_long=True); head_dim 64)")
     parser.add_argument("--recompute_activations", action="store_true",
                         help="with --finetune_encoders: keep one layer's activations at a time (each layer's forward runs again "
                              "in front of its backward: same gradients, ~1/12 of the activation memory, one more forward per step)")
@@ -522,7 +532,14 @@ def build_extractor(args, num_tasks: int = 1, trainable: bool = False) -> Featur
         raise ValueError("--f16_features is for frozen feature extraction in one f16 pass: it excludes --bf16_features, "
                          "--fp8_features, --finetune_encoders, --fp8_finetune and --bf16_finetune")
     if f16 and attention_long:
-        raise ValueError("--f16_features excludes --features_attention_long: there is no key-blocked f16 attention kernel")
+        raise ValueError("--f16_features excludes --features_attention_long (the key-blocked bf16 kernel): the key-blocked f16 "
+                         "attention kernel is switched on by --f16_attention_long")
+    f16_attention_long = bool(getattr(args, "f16_attention_long", False))
+    if f16_attention_long and (fp8_train or bf16_train or trainable):
+        raise ValueError("--f16_attention_long is a switch of frozen f16 feature extraction: it excludes --finetune_encoders, "
+                         "--fp8_finetune and --bf16_finetune")
+    if f16_attention_long and not f16:
+        raise ValueError("--f16_attention_long is a switch of the f16 inference mode: it needs --f16_features")
     if attention_long and not (bf16 or fp8):
         raise ValueError("--features_attention_long is a switch of the inference modes: it needs --bf16_features or --fp8_features")
     recompute = bool(getattr(args, "recompute_activations", False))
@@ -533,7 +550,7 @@ def build_extractor(args, num_tasks: int = 1, trainable: bool = False) -> Featur
     fx = FeatureExtractor(encoder_args(IMAGE_TOWERS.get(tower, tower), **over), encoder_args(TEXT_CONFIG, **over),
                           seq_length=args.seq_length, feat_dim=args.visual_feat_dim, precision=precision,
                           recompute=recompute, bf16_attention=bf16_attention, bf16_attention_long=bf16_attention_long,
-                          attention_long=attention_long)
+                          attention_long=attention_long, f16_attention_long=f16_attention_long)
     text_path, vit_path = getattr(args, "pretrained_model_path", None), getattr(args, "vit_pretrained_model_path", None)
     if text_path or vit_path:
         if not (text_path and vit_path):

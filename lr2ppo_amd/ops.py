@@ -625,6 +625,34 @@ def self_attn_fwd_f16_launch_count() -> int:
     return int(c.value)
 
 
+def self_attn_fwd_f16_blocked(qkv: torch.Tensor, seg, *, batch, heads, L, head_dim, scale, out: Optional[torch.Tensor] = None,
+                              out_plane: Optional[torch.Tensor] = None):
+    """self_attn_fwd_f16 with the keys walked in blocks through LDS (lr2_self_attn_fwd_f16_blocked, csrc/selfattn_f16_blocked.hip): the
+    same arguments, checks and outputs at any L >= 1 -- what the f16 inference schedule runs above 288 tokens with
+    TransformerEncoder.f16_attention_long."""
+    E = heads * head_dim
+    if qkv.element_size() != 2 or not qkv.is_cuda or qkv.numel() < batch * L * 3 * E:
+        raise TypeError("self_attn_fwd_f16_blocked: qkv is a 2-byte HIP tensor [batch * L, 3 * heads * head_dim]")
+    if seg.dtype != torch.int64:
+        raise TypeError("seg must be int64")
+    _chk_f32(out)
+    if out is None and out_plane is None:
+        raise ValueError("self_attn_fwd_f16_blocked: out and / or out_plane")
+    ob = _plane_ptr(out_plane, batch * L * E, "self_attn_fwd_f16_blocked: out_plane") if out_plane is not None else None
+    base = qkv.data_ptr()
+    with _Timed(f"selfattn_f16l_B{batch}_H{heads}_L{L}", 4.0 * batch * heads * L * L * head_dim, 7.0 * batch * L * E):
+        _nat.check(_nat.lib().lr2_self_attn_fwd_f16_blocked(base, base + 2 * E, base + 4 * E, 3 * E, seg.data_ptr(), _ptr(out), ob, E,
+                                                            batch, heads, L, head_dim, scale, _stream()), "lr2_self_attn_fwd_f16_blocked")
+    return out if out is not None else out_plane
+
+
+def self_attn_fwd_f16_blocked_launch_count() -> int:
+    """Accepted self_attn_fwd_f16_blocked calls since the library was loaded (a test hook: which attention a schedule ran)."""
+    c = C.c_uint64(0)
+    _nat.check(_nat.lib().lr2_self_attn_fwd_f16_blocked_launch_count(C.byref(c)), "lr2_self_attn_fwd_f16_blocked_launch_count")
+    return int(c.value)
+
+
 # ---- single-pass bf16 products of encoder training (the "bf16_train" mode, DESIGN 4.6) --------------------------------------------
 _BF16_TRAIN_FORCE_256 = False
 

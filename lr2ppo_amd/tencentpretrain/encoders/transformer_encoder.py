@@ -181,6 +181,10 @@ class TransformerEncoder(nn.Module):
     # operand too, on the key-blocked kernel of csrc/selfattn_mx_blocked.hip (ops.self_attn_fwd_bf16_blocked;
     # FeatureExtractor(precision="bf16" | "mxfp8", attention_long=True)); off: the 3-pass attention kernels above 288
     infer_attention_long = False
+    # True: the f16 inference schedule (forward_f16) runs a layer with head_dim 64 and L > 288 on ONE f16 plane per operand too, on the
+    # key-blocked kernel of csrc/selfattn_f16_blocked.hip (ops.self_attn_fwd_f16_blocked; FeatureExtractor(precision="f16",
+    # f16_attention_long=True)); off: the 3-pass attention kernels above 288
+    f16_attention_long = False
 
     def __init__(self, args):
         super().__init__()
@@ -498,8 +502,9 @@ class TransformerEncoder(nn.Module):
         attention context (ops.self_attn_fwd_f16) and GELU(z) are written as a single f16 plane each by the kernel that produces them; the
         residual stream stays fp32.  The weights are f16 planes of the fp32 parameters (_f16_weights).  The bf16 mode's cost with eight
         times less operand rounding -- FeatureExtractor(precision="f16").
-        L > 288: the 3-pass attention kernels (the QKV product then writes bf16 hi / lo planes, the context goes through ops.round_f16);
-        there is no key-blocked f16 kernel.  Head width below 64 (a multiple of 4): forward_bf16's zero-padded heads on the same kernels.
+        L > 288: the 3-pass attention kernels (the QKV product then writes bf16 hi / lo planes, the context goes through ops.round_f16),
+        or with f16_attention_long the key-blocked single-plane kernel (ops.self_attn_fwd_f16_blocked) on the same single f16 planes: QKV
+        as one plane, no rounding pass over the context.  Head width below 64 (a multiple of 4): forward_bf16's zero-padded heads on the same kernels.
         first_only: -> hidden[:, 0, :] ([batch, hidden]): the last layer computes K | V for every row (an f16 product into hi / lo planes)
         and everything behind the scores for row 0 only (forward_first_token's schedule, B rows: split-bf16)."""
         if emb.dtype != torch.float32 or not emb.is_cuda:
@@ -524,7 +529,8 @@ class TransformerEncoder(nn.Module):
         qkv_p = ws.planes("qkv_p", M, 3 * E)
         x_b, qkv_b, o_b = ws.planes("x_p", M, E).buf[:M * E], qkv_p.buf[:M * 3 * E], ws.planes("o_p", M, E).buf[:M * E]
         t_b, ff_b = ws.planes("t_p", M, E).buf[:M * E], ws.planes("ff_p", M, F).buf[:M * F]
-        fast_attn = hd == 64 and L <= 288
+        fast_attn = hd == 64 and (L <= 288 or self.f16_attention_long)
+        attn_f16 = ops.self_attn_fwd_f16 if L <= 288 else ops.self_attn_fwd_f16_blocked
         h.copy_(emb.contiguous().view(M, E))
         scale = 1.0 / math.sqrt(float(hd))
         if not pre:
@@ -539,7 +545,7 @@ class TransformerEncoder(nn.Module):
                 return self._last_layer_first_token(ws, layer, self._weight_planes(dev)[li], h, None, seg, B, L, E, F, kv_p=kv_p)
             if fast_attn:
                 ops.gemm_f16(x_b, w["wqkv"], None, M, 3 * E, E, bias=w["bqkv"], out_plane=qkv_b)
-                ops.self_attn_fwd_f16(qkv_b, seg, batch=B, heads=H, L=L, head_dim=hd, scale=scale, out_plane=o_b)
+                attn_f16(qkv_b, seg, batch=B, heads=H, L=L, head_dim=hd, scale=scale, out_plane=o_b)
             elif hd != 64:
                 Ep, o32 = H * 64, ws.mat("bf16_o", M, E)
                 pad_p, pad_o = ws.planes("bf16_qkv_pad", M, 3 * Ep), ws.mat("bf16_o_pad", M, Ep)

@@ -5,7 +5,8 @@ from HIP events.  python tools/encoder_bench.py [--batch 32] [--iters 10] [--pas
 the step's peak device memory.  --text-seq L / --only text | image: the text tower at another sequence length / one tower alone.
 --ppo-shapes --precision bf16 | f16 | mxfp8 with --text-seq / --only: the per-tower loop on that inference schedule (forward_bf16 /
 forward_f16 / forward_fp8);
-[--attention-long]: sequences longer than 288 on the key-blocked single-plane attention (TransformerEncoder.infer_attention_long)."""
+[--attention-long]: sequences longer than 288 on the key-blocked single-plane attention (TransformerEncoder.infer_attention_long);
+[--f16-attention-long] (--precision f16): the same on the key-blocked f16 kernel (TransformerEncoder.f16_attention_long)."""
 import argparse
 import os
 import sys
@@ -110,6 +111,9 @@ def parse_args(argv=None):
     ap.add_argument("--attention-long", action="store_true",
                     help="--precision bf16 | mxfp8 (inference): sequences longer than 288 on the key-blocked single-plane attention "
                          "(TransformerEncoder.infer_attention_long) instead of the 3-pass kernels")
+    ap.add_argument("--f16-attention-long", action="store_true",
+                    help="--ppo-shapes --precision f16 (inference): sequences longer than 288 on the key-blocked single-plane f16 "
+                         "attention (TransformerEncoder.f16_attention_long) instead of the 3-pass kernels")
     ap.add_argument("--text-seq", type=int, default=196, help="sequence length of the text tower (at most 514)")
     ap.add_argument("--only", choices=("both", "image", "text"), default="both", help="run one tower alone")
     a = ap.parse_args(argv)
@@ -118,7 +122,10 @@ def parse_args(argv=None):
     if not 1 <= a.text_seq <= ROBERTA["max_seq_length"]:
         ap.error("--text-seq: 1 .. %d" % ROBERTA["max_seq_length"])
     if a.attention_long and (a.train or a.precision not in ("bf16", "mxfp8")):
-        ap.error("--attention-long is a switch of the inference modes: give --precision bf16 | mxfp8, not --train")
+        ap.error("--attention-long is a switch of the inference modes: give --precision bf16 | mxfp8, not --train "
+                 "(--precision f16 has --f16-attention-long)")
+    if a.f16_attention_long and (a.train or not a.ppo_shapes or a.precision != "f16"):
+        ap.error("--f16-attention-long is a switch of the f16 inference mode: give --ppo-shapes --precision f16, not --train")
     if (a.text_seq != 196 or a.only != "both") and a.ppo_shapes and not a.train and a.precision not in ("bf16", "f16", "mxfp8"):
         ap.error("--text-seq / --only are switches of the per-tower loop: not of --ppo-shapes without --train "
                  "(--precision bf16 | f16 | mxfp8 excepted: they then run the per-tower loop on their own schedule)")
@@ -139,7 +146,7 @@ def main():
     ops.set_gemm_passes(a.passes)
     torch.manual_seed(0)
     infer = a.precision if a.precision in ("bf16", "f16", "mxfp8") else None          # (parse_args: never with --train)
-    per_tower = infer is not None and (a.text_seq != 196 or a.only != "both" or a.attention_long)
+    per_tower = infer is not None and (a.text_seq != 196 or a.only != "both" or a.attention_long or a.f16_attention_long)
     if a.ppo_shapes and not a.train and not per_tower:
         prec = "split_bf16" if a.precision == "mxfp8_train" else a.precision      # (a training precision: ignored without --train)
         print(measure_forward(a.batch, iters=a.iters, passes=a.passes, dev=dev, precision=prec))
@@ -162,6 +169,7 @@ def main():
         enc.bf16_attention_long = a.bf16_attention_long
         enc.recompute = a.recompute
         enc.infer_attention_long = a.attention_long
+        enc.f16_attention_long = a.f16_attention_long
         infer_fwd = {"bf16": enc.forward_bf16, "f16": enc.forward_f16, "mxfp8": enc.forward_fp8, None: enc}[infer]
         B = (a.batch * 16 if name.startswith("vit") else a.batch * 2) if a.ppo_shapes else a.batch
         emb = torch.randn(B, L, 768, device=dev, requires_grad=a.train)
@@ -197,7 +205,7 @@ def main():
         for k, v in prof.items():
             c = k.split("_")[0] + ("_" + k.split("_")[1] if k.startswith("gemm") else "")
             classes[c] = classes.get(c, 0.0) + v["ms"]
-        print(f"{name:13s} B={B} L={L} {a.precision if a.train or infer else ''}{' attention-long' if a.attention_long else ''}: {ms:7.3f} ms/{'step' if a.train else 'forward'}  {fl / ms / 1e9:7.1f} TFLOP/s (algorithmic)  "
+        print(f"{name:13s} B={B} L={L} {a.precision if a.train or infer else ''}{' attention-long' if a.attention_long else ''}{' f16-attention-long' if a.f16_attention_long else ''}: {ms:7.3f} ms/{'step' if a.train else 'forward'}  {fl / ms / 1e9:7.1f} TFLOP/s (algorithmic)  "
               f"frac of 2.5 PF bf16 dense x{passes} passes: {passes * fl / ms / 1e9 / 2500:.3f}", flush=True)
         if a.train:
             print(f"    recompute {'on' if a.recompute else 'off'}: peak memory {peak / 2 ** 30:.2f} GiB ({(peak - resident) / 2 ** 30:.2f} GiB above "
