@@ -393,6 +393,13 @@ int lr2_vit_assemble(const void* patch_proj, const void* cls, const void* pos, v
  *                    the A operand of the next product without an fp32 round trip.  out_hi / out_lo_off / ld_planes: the result also /
  *                    instead as bf16 hi / lo planes (the operand format of lr2_self_attn_fwd and of the split-bf16 products);
  *                    out_lo_off == 0 (ABI 18): ONE bf16 plane (round to nearest even), the operand format of lr2_self_attn_fwd_bf16.
+ * Every producer of the format in this library (these two, lr2_layernorm_fwd_mxfp8, lr2_quant_mxfp8_t, lr2_self_attn_fwd_bf16 and its
+ * blocked form) writes the same bytes for the same fp32 row: scale byte = max(exponent field of amax - 8, 0): 0 for amax below 2^-118, 247 for
+ * amax = Inf; a NaN element takes no part in amax and becomes 0xFE (-448), +-Inf +-448, -0 and negative values
+ * that round to zero 0x80; fp32 denormals are not flushed (tests/test_mx_edges_gpu.py).
+ * LR2_ERR_ARG: a NULL operand; no destination; act other than 0 / 1; out_q without out_scales or the reverse; non-positive sizes.
+ * LR2_ERR_SHAPE: lr2_quant_mxfp8: K % 32, ldx < K, ldx % 4; lr2_gemm_mxfp8: N % 128, K % 128, ld_out or ld_resid below N or no multiple
+ * of 4 (where the pointer is given), ld_planes below N or no multiple of 4, out_lo_off % 4.  A refused call writes nothing.
  * replaces: nn.Linear forward (tencentpretrain/layers/position_ffn.py:12-15, multi_headed_attn.py:55-76) in that mode. */
 int lr2_quant_mxfp8(const void* x, int ldx, void* q, void* scales, int rows, int K, void* stream);
 /* LayerNorm (lr2_layernorm_fwd's semantics, modes 0 / 1) whose result leaves as MX-FP8 [rows, D] + [rows, D / 32] (and as fp32 when out is
@@ -628,7 +635,9 @@ int lr2_quant_mxfp8_t(const void* x, int is_planes, uint64_t lo_off, int ldx, co
 /*   lr2_gemm_mxfp8_wgrad: out[M, ld_out] (+)= A_q . B_q^T with A_q [M, K], B_q [N, K] as lr2_quant_mxfp8_t writes them (K = the padded
  *                      token count); `splits` K slices (capped at K / 128) leave fp32 partials in workspace [splits, M, N] that one more
  *                      launch sums in slice order: the same bits on every run.  splits == 1: no workspace.  M, N, K % 128 == 0;
- *                      out and workspace 16-byte aligned.
+ *                      out and workspace 16-byte aligned.  LR2_ERR_SHAPE: M, N or K % 128, ld_out < N, ld_out % 4, alignment;
+ *                      LR2_ERR_ARG: a NULL operand or out, splits < 1, more than one (capped) slice without a workspace; a refused
+ *                      call writes nothing.
  * replaces: the TN weight-gradient products of planes (lr2_gemm with trans_a = trans_b = 1), in that mode. */
 int lr2_gemm_mxfp8_wgrad(const void* a_q, const void* a_scales, const void* b_q, const void* b_scales, void* out, int ld_out,
                          int accumulate, void* workspace, int splits, int M, int N, int K, void* stream);
