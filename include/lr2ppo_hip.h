@@ -572,9 +572,31 @@ int lr2_self_attn_fwd_bf16_blocked_launch_count(uint64_t* count);
  * replaces: nn.Linear forward (tencentpretrain/layers/position_ffn.py:12-15, multi_headed_attn.py:55-76) in that mode. */
 int lr2_gemm_f16(const void* A, const void* B, int M, int N, int K, int lda, int ldb, uint64_t a_bytes, uint64_t b_bytes,
                  const lr2_epilogue* epi, void* stream);
-/* Diagnostic: *count = accepted lr2_gemm_f16 calls since the library was loaded (a plain host counter, not synchronised).
+/* Diagnostic: *count = accepted lr2_gemm_f16 and lr2_gemm_f16_tiled calls since the library was loaded, one per call (a plain host
+ * counter, not synchronised).
  * replaces: nothing (a test hook, as lr2_gemm_bf16_launch_counts). */
 int lr2_gemm_f16_launch_count(uint64_t* count);
+/* Added within ABI 27 (purely additive: no signature or struct changes).  lr2_gemm_f16's product with lr2_gemm_bf16's parameter list
+ * and dispatch: the same operands, epilogue contract, argument checks and return codes as lr2_gemm_f16, and
+ *   block_m == 256: the 256 x 256 f16 kernel under lr2_gemm_row_split_plan, as lr2_gemm_bf16 does it -- the leading whole rounds of the
+ *       chip on csrc/gemm256_f16.hip, the remaining rows on the 128- / 64-row f16 kernels (A and every set epilogue pointer advanced by
+ *       the plan's rows of its own leading dimension); no plan: lr2_gemm_f16's single launch.  LR2_ERR_SHAPE for a_bytes / b_bytes
+ *       > 4 GiB - 768 B (that kernel's limit; only this block_m checks it).
+ *   block_m == 128 / 64: the whole product on the f16 instantiations of the general kernel family (csrc/gemm.hip: 128 x 128 / 64 x 128
+ *       tiles, 4 waves, one v_mfma_f32_16x16x32_f16 product per tile pair); any other block_m is treated as 128 (the family's rule).
+ *       LR2_ERR_SHAPE for a_bytes / b_bytes >= 4 GiB (lr2_gemm_bf16's rule).
+ * Each accumulator runs through k in ascending 32-wide MFMA steps in either kernel and the epilogue code is shared, so the tile height
+ * changes no result bit (tests assert it).  lr2_gemm_f16_launch_count counts the accepted calls of lr2_gemm_f16 AND of this entry point,
+ * one per call.  Nothing is launched (and nothing counted) by a rejected call.
+ * replaces: nn.Linear forward (tencentpretrain/layers/position_ffn.py:12-15, multi_headed_attn.py:55-76) in that mode, at the sizes
+ * where a launch is not many whole rounds of 256-row tiles; lr2_gemm_f16 is unchanged. */
+int lr2_gemm_f16_tiled(const void* A, const void* B, int M, int N, int K, int lda, int ldb, uint64_t a_bytes, uint64_t b_bytes,
+                       const lr2_epilogue* epi, int block_m, void* stream);
+/* Diagnostic (added within ABI 27): kernel launches issued by lr2_gemm_f16 and lr2_gemm_f16_tiled since the library was loaded --
+ * counts[0] the 256 x 256 f16 kernel, counts[1] the f16 kernels of the general family; a row-split call adds one to each (no device
+ * call; plain host counters, not synchronised).
+ * replaces: nothing (a test hook, as lr2_gemm_bf16_launch_counts). */
+int lr2_gemm_f16_launch_counts(uint64_t counts[2]);
 /* lr2_layernorm_fwd with the single plane in f16: the arguments of its out_lo_off = 0 form (out fp32 and / or out_f16, optional mean /
  * rstd, mode 0 = nn.LayerNorm / 1 = the TencentPretrain LayerNorm, the group / group_stride row map).  D % 4 == 0, D <= 1024.
  * replaces: tencentpretrain/layers/layer_norm.py:5-21 (and nn.LayerNorm, finetune/xit.py:37) in front of a product of that mode. */

@@ -155,6 +155,8 @@ SIGNATURES = {
     "lr2_self_attn_fwd_bf16_blocked_launch_count": [C.POINTER(C.c_uint64)],
     "lr2_gemm_f16": [_P, _P, _I, _I, _I, _I, _I, _U64, _U64, C.POINTER(Epilogue), _P],
     "lr2_gemm_f16_launch_count": [C.POINTER(C.c_uint64)],
+    "lr2_gemm_f16_tiled": [_P, _P, _I, _I, _I, _I, _I, _U64, _U64, C.POINTER(Epilogue), _I, _P],
+    "lr2_gemm_f16_launch_counts": [C.POINTER(C.c_uint64)],
     "lr2_layernorm_fwd_f16": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _I, _I, _U64, _P],
     "lr2_round_f16": [_P, _P, _U64, _P],
     "lr2_self_attn_fwd_f16": [_P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P],

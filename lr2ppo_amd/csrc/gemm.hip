@@ -276,7 +276,9 @@ __device__ __forceinline__ void pin_pipeline() {
 // One K-tile of MFMA work for a wave.  Fragment reads run one MFMA group ahead of their use (register double
 // buffering, pinned with sched_group_barrier: hipcc otherwise sinks every read to its first use and drains
 // lgkmcnt(0) ten times per tile).
-template <int BM, int BN, int BK, int MI, int NI, bool TA, bool TB, int PASSES>
+// F16 (PASSES == 1 only): the product is v_mfma_f32_16x16x32_f16 -- the f16 MFMA has the bf16 one's operand bytes and fragment map
+// (gemm256_f16.hip), so the images, the reads and the pinned order are the bf16 ones and only the instruction gives the bytes a format.
+template <int BM, int BN, int BK, int MI, int NI, bool TA, bool TB, int PASSES, bool F16 = false>
 __device__ __forceinline__ void compute_tile(const char* a_hi, const char* b_hi, int wm0, int wn0, int lane,
                                              f32x4_t (&acc)[MI][NI]) {
   constexpr int A_TILE = BM * BK * 2, B_TILE = BN * BK * 2;
@@ -314,7 +316,13 @@ __device__ __forceinline__ void compute_tile(const char* a_hi, const char* b_hi,
         }
       }
 #pragma unroll
-      for (int i = 0; i < MI; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[ks][i], bh[cur], acc[i][j], 0, 0, 0);
+      for (int i = 0; i < MI; ++i) {
+        if constexpr (F16)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, ah[ks][i]), __builtin_bit_cast(f16x8_t, bh[cur]),
+                                                             acc[i][j], 0, 0, 0);
+        else
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[ks][i], bh[cur], acc[i][j], 0, 0, 0);
+      }
     }
   }
   constexpr int NIMGS = PASSES == 3 ? 2 : 1;
@@ -325,12 +333,16 @@ __device__ __forceinline__ void compute_tile(const char* a_hi, const char* b_hi,
 
 // ---- the kernel ------------------------------------------------------------------------------------
 // (EXACT: the two instantiations lr2_gemm_bf16_train launches for act == 2 -- the epilogue multiplies by gemm_common.h::mul_gelu_grad_exact)
-template <int BM, int BN, int BK, int WM, int WN, bool TA, bool TB, int PASSES, bool APL, bool BPL, int NW = 4, bool EXACT = false>
+// (F16: the two instantiations lr2_gemm_f16_tiled launches -- single f16 planes: the f16 MFMA, and gemm_common.h's F16 plane writer)
+template <int BM, int BN, int BK, int WM, int WN, bool TA, bool TB, int PASSES, bool APL, bool BPL, int NW = 4, bool EXACT = false,
+          bool F16 = false>
 // 8-wave workgroups are meant to run two per CU = 4 waves per SIMD: cap the register allocation at 128 for them
 __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 1) void gemm_kernel(GemmParams g) {
   static_assert(NW == 4 || (APL && BPL), "8-wave workgroups exist for planes x planes operands only");
   static_assert(BK == 64 || (APL && BPL), "32-deep tiles exist for planes x planes operands only");
   static_assert((BM / WM) * (BN / WN) == NW, "wave grid");
+  static_assert(!F16 || (APL && BPL && !TA && !TB && PASSES == 1 && NW == 4 && BK == 64 && !EXACT),
+                "f16 planes: planes x planes, NT, one pass, 4 waves, 64-deep K tiles (one LDS stage: launch_f16)");
   constexpr int MI = WM / 16, NI = WN / 16;
   constexpr int WAVES_N = BN / WN;
   constexpr int NIMG = PASSES == 3 ? 2 : 1;
@@ -419,7 +431,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 1) void gemm_kernel(GemmPara
     if constexpr ((APL || BPL) && (TA || TB))
       compute_tile_preload<BM, BN, BK, MI, NI, TA, TB, PASSES>(a_cur, b_cur, wm0, wn0, lane, acc);
     else
-      compute_tile<BM, BN, BK, MI, NI, TA, TB, PASSES>(a_cur, b_cur, wm0, wn0, lane, acc);
+      compute_tile<BM, BN, BK, MI, NI, TA, TB, PASSES, F16>(a_cur, b_cur, wm0, wn0, lane, acc);
     if (!APL || !BPL || !dbuf) {
       __syncthreads();  // every wave is done reading the single-buffered image(s)
       if (more) {
@@ -437,7 +449,9 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 1) void gemm_kernel(GemmPara
   float* slab = reinterpret_cast<float*>(smem) + wave * (32 * (WN + 4));
   float* part = g.partial ? g.partial + (size_t)split * (size_t)g.M * (size_t)g.N : nullptr;
   if (g.epi.adam_p && !part) epilogue_wave_adam<WM, WN, MI, NI, ((APL && BPL) ? (NW == 8 ? 1 : 0) : -1)>(g, acc, slab, m0 + wm0, n0 + wn0, lane);
-  else epilogue_wave<WM, WN, MI, NI, 3, ((APL && BPL) ? (NW == 8 ? 1 : 0) : -1), EXACT>(g, acc, slab, m0 + wm0, n0 + wn0, lane, part);
+  // (F16: the straight-line forms of the single-plane inference kernels, WIDE 3 -- a single f16 plane is what QKV and FFN-1 write, and
+  //  the general per-element path costs such a launch 13-30 %: DESIGN.md 4)
+  else epilogue_wave<WM, WN, MI, NI, 3, (F16 ? 3 : (APL && BPL) ? (NW == 8 ? 1 : 0) : -1), EXACT, F16>(g, acc, slab, m0 + wm0, n0 + wn0, lane, part);
 }
 
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ partial, int splits, int M, int N,
@@ -478,6 +492,8 @@ constexpr int gemm_bk(bool apl, bool bpl, bool tb) { return (apl && bpl && tb) ?
   LR2_GEMM_INST_FORM(true, true, APL, BPL)
 template __global__ void gemm_kernel<64, 128, 64, 64, 32, false, false, 1, true, true, 4, true>(GemmParams);     // lr2_gemm_bf16_train, act == 2
 template __global__ void gemm_kernel<128, 128, 64, 64, 64, false, false, 1, true, true, 4, true>(GemmParams);
+template __global__ void gemm_kernel<64, 128, 64, 64, 32, false, false, 1, true, true, 4, false, true>(GemmParams);    // lr2_gemm_f16_tiled
+template __global__ void gemm_kernel<128, 128, 64, 64, 64, false, false, 1, true, true, 4, false, true>(GemmParams);
 LR2_GEMM_INST_FORMS(false, false)
 LR2_GEMM_INST_FORMS(true, false)
 LR2_GEMM_INST_FORM(true, true, true, true)
@@ -546,6 +562,27 @@ int launch_exact(const GemmParams& p_in, hipStream_t stream) {
   static bool attr_set = false;
   if (!attr_set) {
     if (lr2_allow_dynamic_lds(kern, lds, "gemm(exact GELU')")) return LR2_ERR_LAUNCH;
+    attr_set = true;
+  }
+  LR2_LAUNCH(kern, dim3(p.tiles_m * p.tiles_n), dim3(64 * NW), lds, stream, p);
+  return lr2_launch_status(__func__);
+}
+
+// lr2_gemm_f16_tiled: launch<BM, false, false, 1, true, true> on the F16 instantiation
+template <int BM>
+int launch_f16(const GemmParams& p_in, hipStream_t stream) {
+  constexpr int BN = 128, BK = 64, NW = 4, WN = BM == 128 ? 64 : 32;
+  GemmParams p = p_in;
+  p.tiles_m = (p.M + BM - 1) / BM;
+  p.tiles_n = (p.N + BN - 1) / BN;
+  p.splits = 1;
+  p.dma_stages = 1;
+  constexpr size_t main_lds = (size_t)(BM + BN) * BK * 2, epi_lds = (size_t)NW * 32 * (WN + 4) * 4;
+  constexpr size_t lds = main_lds > epi_lds ? main_lds : epi_lds;
+  auto kern = gemm_kernel<BM, BN, BK, 64, WN, false, false, 1, true, true, NW, false, true>;
+  static bool attr_set = false;
+  if (!attr_set) {
+    if (lr2_allow_dynamic_lds(kern, lds, "gemm(f16)")) return LR2_ERR_LAUNCH;
     attr_set = true;
   }
   LR2_LAUNCH(kern, dim3(p.tiles_m * p.tiles_n), dim3(64 * NW), lds, stream, p);
@@ -841,8 +878,10 @@ extern "C" int lr2_gemm_bf16(const void* A, const void* B, int M, int N, int K, 
   return launch_gemm256_b1(p, s);
 }
 
-// ---- single-pass f16 products of ONE plane per operand (the "f16" inference mode): the 256 x 256 kernel of gemm256_f16.hip at every size ----
-static uint64_t g_launches_f16 = 0;
+// ---- single-pass f16 products of ONE plane per operand (the "f16" inference mode): lr2_gemm_f16 = the 256 x 256 kernel of
+// gemm256_f16.hip at every size; lr2_gemm_f16_tiled = lr2_gemm_bf16's dispatch over that kernel and the F16 128- / 64-row kernels ----
+static uint64_t g_launches_f16 = 0;            // accepted calls of both entry points
+static uint64_t g_launches_f16_k[2] = {0, 0};  // kernel launches: the 256 x 256 f16 kernel, the general family's F16 instantiations
 extern "C" int lr2_gemm_f16_launch_count(uint64_t* count) {
   if (!count) return LR2_ERR_ARG;
   *count = g_launches_f16;
@@ -873,7 +912,71 @@ extern "C" int lr2_gemm_f16(const void* A, const void* B, int M, int N, int K, i
   p.epi = to_device_epilogue(epi);
   p.epi.store_nt = (uint64_t)M * (uint64_t)N * (epi->out ? 4ull : 2ull) >= (256ull << 20) ? 1 : 0;   // lr2_gemm_bf16's rule
   ++g_launches_f16;
+  ++g_launches_f16_k[0];
   return launch_gemm256_f16(p, (hipStream_t)stream);
+}
+
+extern "C" int lr2_gemm_f16_launch_counts(uint64_t counts[2]) {
+  if (!counts) return LR2_ERR_ARG;
+  counts[0] = g_launches_f16_k[0];
+  counts[1] = g_launches_f16_k[1];
+  return 0;
+}
+
+extern "C" int lr2_gemm_f16_tiled(const void* A, const void* B, int M, int N, int K, int lda, int ldb, uint64_t a_bytes, uint64_t b_bytes,
+                                  const lr2_epilogue* epi, int block_m, void* stream) {
+  // lr2_gemm_f16's checks and return codes
+  if (!A || !B || M <= 0 || N <= 0 || K <= 0 || !epi || (!epi->out && !epi->out_hi)) return LR2_ERR_ARG;
+  if (epi->drop_p > 0.f || epi->act < 0 || epi->act > 1 || epi->accumulate || epi->out_z || epi->adam_p || epi->colsum) return LR2_ERR_ARG;
+  if (K % 64) return LR2_ERR_SHAPE;             // whole 64-deep K steps on the 256 x 256 kernel AND on the 128- / 64-row family
+  if ((lda % 8) || (ldb % 8) || (N % 4)) return LR2_ERR_SHAPE;
+  if ((epi->out && epi->ld_out % 4) || (epi->resid && epi->ld_resid % 4) || (epi->out_hi && epi->ld_planes % 4)) return LR2_ERR_SHAPE;
+  if (gemm_ld_too_small(epi, M, N, K, lda, ldb, 0, 0)) return LR2_ERR_SHAPE;
+  const bool want256 = block_m == 256;
+  if (a_bytes >= (1ull << 32) || b_bytes >= (1ull << 32)) return LR2_ERR_SHAPE;     // 32-bit buffer extents
+  // the ring's 32-bit source offsets: lr2_gemm_f16's limit, for the call that asks for its kernel (not a silent change of kernel)
+  if (want256 && (a_bytes > 0xFFFFFD00ull || b_bytes > 0xFFFFFD00ull)) return LR2_ERR_SHAPE;
+  if (block_m != 64) block_m = 128;
+  GemmParams p{};
+  p.A = A;
+  p.B = B;
+  p.M = M;
+  p.N = N;
+  p.K = K;
+  p.lda = lda;
+  p.ldb = ldb;
+  p.a_bytes = (uint32_t)a_bytes;
+  p.b_bytes = (uint32_t)b_bytes;
+  p.k_tiles_per_split = K / 64;
+  p.epi = to_device_epilogue(epi);
+  p.epi.store_nt = (uint64_t)M * (uint64_t)N * (epi->out ? 4ull : 2ull) >= (256ull << 20) ? 1 : 0;   // lr2_gemm_f16's rule
+  hipStream_t s = (hipStream_t)stream;
+  ++g_launches_f16;
+  if (!want256) {
+    ++g_launches_f16_k[1];
+    return block_m == 64 ? launch_f16<64>(p, s) : launch_f16<128>(p, s);
+  }
+  // the row split of lr2_gemm_bf16 (lr2_gemm_row_split_plan): whole rounds of the chip on the 256 x 256 kernel, the rest on short tiles
+  int M1 = 0, bm2 = 128;
+  if (lr2_gemm_row_split_plan(M, N, K, &M1, &bm2) == 0 && M1 > 0) {
+    GemmParams p1 = p;
+    p1.M = M1;
+    const int rc = launch_gemm256_f16(p1, s);
+    if (rc) return rc;
+    ++g_launches_f16_k[0];
+    ++g_launches_f16_k[1];
+    GemmParams p2 = p;
+    p2.M = M - M1;
+    p2.A = (const char*)A + (size_t)M1 * (size_t)lda * 2u;
+    p2.a_bytes = (uint32_t)(a_bytes - (uint64_t)M1 * (uint64_t)lda * 2u);
+    Epilogue& e2 = p2.epi;
+    if (e2.resid) e2.resid += (size_t)M1 * e2.ld_resid;
+    if (e2.out) e2.out += (size_t)M1 * e2.ld_out;
+    if (e2.out_hi) e2.out_hi += (size_t)M1 * e2.ld_planes;
+    return bm2 == 64 ? launch_f16<64>(p2, s) : launch_f16<128>(p2, s);
+  }
+  ++g_launches_f16_k[0];
+  return launch_gemm256_f16(p, s);
 }
 
 // ---- single-pass bf16 products of encoder training (the "bf16_train" mode): forward / input gradient (NT) and weight gradient (TN) ----

@@ -534,11 +534,14 @@ def gemm_bf16_launch_counts():
 def gemm_f16(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor], M: int, N: int, K: int, *,
              lda: Optional[int] = None, ldb: Optional[int] = None, ld_out: Optional[int] = None, bias: Optional[torch.Tensor] = None,
              act: int = 0, resid: Optional[torch.Tensor] = None, alpha: float = 1.0, out_plane: Optional[torch.Tensor] = None,
-             out_planes: Optional[Planes] = None, planes_col: int = 0):
+             out_planes: Optional[Planes] = None, planes_col: int = 0, block_m: Optional[int] = None):
     """out[M, N] = a[M, K] @ b[N, K]^T (+ bias) (act 1: GELU) (+ resid) as ONE f16 pass (lr2_gemm_f16): a, b are single f16 planes
     (2-byte HIP tensors: what round_f16, layernorm_fwd_f16, self_attn_fwd_f16 and this product write).  The result goes to `out`
     (fp32) and / or ONE f16 plane `out_plane` (clamped to +-65504, round to nearest even) or bf16 hi / lo `out_planes` (the operands of
-    the 3-pass attention kernels).  Inference only: the f16 mode, never the parity path.  The 256 x 256 kernel at every size.
+    the 3-pass attention kernels).  Inference only: the f16 mode, never the parity path.
+    block_m: None = lr2_gemm_f16, the 256 x 256 kernel at every size; 256 = that kernel under the row split of gemm_bf16 (whole rounds
+    of the chip there, the remaining rows on short tiles), 128 / 64 = the f16 kernels of the general family (lr2_gemm_f16_tiled).  The
+    tile height changes no result bit; f16_block_m is the measured rule the schedule follows.
     planes_col: as gemm_bf16."""
     _chk_f32(out, bias, resid)
     lda = K if lda is None else lda
@@ -558,17 +561,87 @@ def gemm_f16(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor], M: i
         e.out_hi, e.out_lo_off, e.ld_planes = out_planes.data_ptr() + 2 * planes_col, out_planes.lo_off, out_planes.cols
     e.act, e.alpha = act, alpha
     with _Timed(f"gemm_f16_M{M}_N{N}_K{K}", 2.0 * M * N * K, 2.0 * (M * K + N * K) + (4.0 if out is not None else 2.0) * M * N):
-        rc = _nat.lib().lr2_gemm_f16(a_ptr, b_ptr, M, N, K, lda, ldb, a.numel() * 2, b.numel() * 2, C.byref(e), _stream())
+        if block_m is None:
+            rc = _nat.lib().lr2_gemm_f16(a_ptr, b_ptr, M, N, K, lda, ldb, a.numel() * 2, b.numel() * 2, C.byref(e), _stream())
+        else:
+            if block_m not in (256, 128, 64):
+                raise ValueError("gemm_f16: block_m is None, 256, 128 or 64")
+            rc = _nat.lib().lr2_gemm_f16_tiled(a_ptr, b_ptr, M, N, K, lda, ldb, a.numel() * 2, b.numel() * 2, C.byref(e), block_m,
+                                               _stream())
     if rc:
-        _nat.check(rc, f"lr2_gemm_f16(M={M},N={N},K={K})")
+        _nat.check(rc, f"lr2_gemm_f16(M={M},N={N},K={K},block_m={block_m})")
     return out if out is not None else (out_plane if out_plane is not None else out_planes)
 
 
 def gemm_f16_launch_count() -> int:
-    """Accepted lr2_gemm_f16 calls since the library was loaded."""
+    """Accepted lr2_gemm_f16 and lr2_gemm_f16_tiled calls since the library was loaded (one per call)."""
     c = C.c_uint64(0)
     _nat.check(_nat.lib().lr2_gemm_f16_launch_count(C.byref(c)), "lr2_gemm_f16_launch_count")
     return int(c.value)
+
+
+def gemm_f16_launch_counts():
+    """(launches of the 256 x 256 f16 kernel, launches of the f16 kernels of the general family) by gemm_f16 since the library was
+    loaded; a row-split call adds one to each."""
+    c = (C.c_uint64 * 2)()
+    _nat.check(_nat.lib().lr2_gemm_f16_launch_counts(c), "lr2_gemm_f16_launch_counts")
+    return int(c[0]), int(c[1])
+
+
+_F16_FORCE_256 = False
+
+
+@contextlib.contextmanager
+def f16_force_256():
+    """Inside the block f16_block_m is bypassed: the f16 schedule (TransformerEncoder.forward_f16) passes block_m = None, i.e. every
+    product is one lr2_gemm_f16 call on the 256 x 256 kernel (what tests compare the dispatched schedule with, bit for bit)."""
+    global _F16_FORCE_256
+    prev, _F16_FORCE_256 = _F16_FORCE_256, True
+    try:
+        yield
+    finally:
+        _F16_FORCE_256 = prev
+
+
+def f16_schedule_block_m(M: int, N: int, K: int) -> Optional[int]:
+    """The block_m the f16 schedule passes to gemm_f16: f16_block_m's, or None inside f16_force_256()."""
+    return None if _F16_FORCE_256 else f16_block_m(M, N, K)
+
+
+@functools.lru_cache(maxsize=4096)
+def f16_block_m(M: int, N: int, K: int) -> int:
+    """Tile height (256, 128 or 64) of a single-pass f16 product: the block_m gemm_f16 gets from the f16 schedule.  256 = the 256 x 256
+    kernel under the row split (lr2_gemm_row_split_plan), 128 / 64 = the f16 kernels of the general family.  The tile height changes no
+    result bit (tests/test_f16_tiles_gpu.py), so the rule is about time only.
+    Fitted to tools/gemm_bench.py --f16 --f16-schedule-epilogues {--f16-unsplit, --bm 256, --bm 128, --bm 64} --iters 200 on MI355X --
+    every product with the epilogue and destination forward_f16 gives it (N = 4 K: bias, GELU -> one f16 plane; N = 3 K: bias -> one
+    f16 plane; else bias + residual -> fp32) --, a fresh process per run, the four variants alternating, each twice; us, mean of the
+    two runs: lr2_gemm_f16 (one launch of the 256 x 256 kernel: what every product paid before) / block_m 256 (the row split where the
+    plan has one) / 128 / 64 -> the rule's answer:
+      M=100864 N=3072 K=768: 624.6 / 623.5 / 735.9 / 799.0 -> 256
+      M=100864 N=768 K=3072: 484.8 / 485.2 / 713.9 / 761.9 -> 256
+      M=100864 N=2304 K=768: 399.6 / 398.0 / 496.4 / 562.1 -> 256
+      M=12544 N=3072 K=768: 102.3 / 96.5 / 112.9 / 115.8 -> 256     (588 tiles = 2.3 rounds: the row split, 10 752 rows + 1792 on 64-row tiles)
+      M=12544 N=768 K=3072: 74.4 / 74.0 / 112.1 / 91.2 -> 256       (147 tiles: 192-row tiles)
+      M=12544 N=2304 K=768: 59.1 / 58.8 / 73.8 / 72.9 -> 256        (441 tiles)
+      M=12544 N=768 K=768: 28.9 / 28.8 / 43.9 / 34.7 -> 256         (147 tiles)
+      M=6304 N=2304 K=768: 30.1 / 30.1 / 38.6 / 41.4 -> 256         (225 tiles)
+      M=6304 N=3072 K=768: 62.0 / 53.7 / 58.7 / 59.0 -> 256         (300 tiles = 1.2 rounds: the row split, 5376 rows + 928 on 64-row tiles)
+      M=6304 N=768 K=768: 24.4 / 24.4 / 23.8 / 19.1 -> 64           (75 tiles)
+      M=6304 N=768 K=3072: 64.0 / 64.3 / 55.9 / 46.6 -> 64          (75 tiles)
+    Spread between the two runs of one variant: at most 2.8 % (73.9 / 71.9), typically 0.3 %.  A shape class leaves lr2_gemm_f16's single
+    launch only where the other form is ahead by more than that: the row split wherever the plan has one (- 6 % and - 13 %), 64-row
+    tiles below half a round of 256 x 256 tiles (- 22 % and - 27 %); 128-row tiles win nowhere.  This is NOT use_gemm256_b1's rule: with
+    the result leaving as one 2-byte plane the 256 x 256 kernel is 25-35 % faster than with an fp32 result and the short tiles gain
+    less, so just over one round (256 < tiles < 384) the row split beats whole launches of 64-row tiles here.  (With a bare fp32 result
+    -- the same command without --f16-schedule-epilogues -- M = 6304, N = 3072 reads 79.7 / 66.8 / 70.9 / 61.4: 64 rows would win by 8 %;
+    the schedule never asks for that form at that width.  DESIGN 4 has that table.)  The 128-tile boundary is use_gemm256_b1's: measured on
+    either side of it (75 and 147 tiles), not at it.
+    K % 64 != 0 (never in the schedule; either kernel refuses it): a short tile, never the ring."""
+    if K % 64:
+        return 64                                       # (refused by either kernel; never the 256 x 256 ring)
+    tiles = ((M + 255) // 256) * ((N + 255) // 256)
+    return 256 if tiles >= 128 else 64
 
 
 def layernorm_fwd_f16(x, gamma, beta, rows, D, eps, mode, *, group=0, group_stride=0, out=None, mean=None, rstd=None,

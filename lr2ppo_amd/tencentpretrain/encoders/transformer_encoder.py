@@ -497,8 +497,8 @@ class TransformerEncoder(nn.Module):
 
     @torch.no_grad()
     def forward_f16(self, emb, seg, first_only: bool = False):
-        """forward(emb, seg) with every GEMM operand ONE f16 plane and every projection ONE f16 pass (ops.gemm_f16,
-        csrc/gemm256_f16.hip): forward_bf16's schedule -- the LayerNorm output (ops.layernorm_fwd_f16), Q | K | V as one [M, 3E] plane, the
+        """forward(emb, seg) with every GEMM operand ONE f16 plane and every projection ONE f16 pass (ops.gemm_f16:
+        csrc/gemm256_f16.hip or the f16 short tiles of csrc/gemm.hip by ops.f16_block_m, the same bits either way): forward_bf16's schedule -- the LayerNorm output (ops.layernorm_fwd_f16), Q | K | V as one [M, 3E] plane, the
         attention context (ops.self_attn_fwd_f16) and GELU(z) are written as a single f16 plane each by the kernel that produces them; the
         residual stream stays fp32.  The weights are f16 planes of the fp32 parameters (_f16_weights).  The bf16 mode's cost with eight
         times less operand rounding -- FeatureExtractor(precision="f16").
@@ -533,6 +533,7 @@ class TransformerEncoder(nn.Module):
         attn_f16 = ops.self_attn_fwd_f16 if L <= 288 else ops.self_attn_fwd_f16_blocked
         h.copy_(emb.contiguous().view(M, E))
         scale = 1.0 / math.sqrt(float(hd))
+        bm = lambda N, K: ops.f16_schedule_block_m(M, N, K)            # noqa: E731  (tile height by the measured rule; None in f16_force_256)
         if not pre:
             ops.round_f16(h, x_b)                                     # the first layer's operand
         for li, (layer, w) in enumerate(zip(self.transformer, W)):
@@ -541,10 +542,10 @@ class TransformerEncoder(nn.Module):
                 ops.layernorm_fwd_f16(h, ln1.gamma.data, ln1.beta.data, rows=M, D=E, eps=ln1.eps, mode=1, out_plane=x_b)
             if first_only and li == self.layers_num - 1:
                 kv_p = ws.planes("kv_p", M, 2 * E)
-                ops.gemm_f16(x_b, w["wqkv"][E * E:], None, M, 2 * E, E, bias=w["bqkv"][E:], out_planes=kv_p)
+                ops.gemm_f16(x_b, w["wqkv"][E * E:], None, M, 2 * E, E, bias=w["bqkv"][E:], out_planes=kv_p, block_m=bm(2 * E, E))
                 return self._last_layer_first_token(ws, layer, self._weight_planes(dev)[li], h, None, seg, B, L, E, F, kv_p=kv_p)
             if fast_attn:
-                ops.gemm_f16(x_b, w["wqkv"], None, M, 3 * E, E, bias=w["bqkv"], out_plane=qkv_b)
+                ops.gemm_f16(x_b, w["wqkv"], None, M, 3 * E, E, bias=w["bqkv"], out_plane=qkv_b, block_m=bm(3 * E, E))
                 attn_f16(qkv_b, seg, batch=B, heads=H, L=L, head_dim=hd, scale=scale, out_plane=o_b)
             elif hd != 64:
                 Ep, o32 = H * 64, ws.mat("bf16_o", M, E)
@@ -555,25 +556,26 @@ class TransformerEncoder(nn.Module):
                     for hh in range(H):
                         r0 = blk * E + hh * hd                        # rows of [Wq; Wk; Wv] = this head's output columns
                         ops.gemm_f16(x_b, w["wqkv"][r0 * E:(r0 + hd) * E], None, M, hd, E, bias=w["bqkv"][r0:r0 + hd],
-                                     out_planes=pad_p, planes_col=blk * Ep + hh * 64)
+                                     out_planes=pad_p, planes_col=blk * Ep + hh * 64, block_m=bm(hd, E))
                 ops.self_attn_fwd(pad_p, seg, pad_o, batch=B, heads=H, L=L, head_dim=64, scale=scale)
                 o32.copy_(pad_o.view(M, H, 64)[:, :, :hd].reshape(M, E))
                 ops.round_f16(o32, o_b)
             else:
                 o32 = ws.mat("bf16_o", M, E)
-                ops.gemm_f16(x_b, w["wqkv"], None, M, 3 * E, E, bias=w["bqkv"], out_planes=qkv_p)     # the 3-pass kernels take hi / lo planes
+                ops.gemm_f16(x_b, w["wqkv"], None, M, 3 * E, E, bias=w["bqkv"], out_planes=qkv_p,     # the 3-pass kernels take hi / lo planes
+                             block_m=bm(3 * E, E))
                 ops.self_attn_fwd(qkv_p, seg, o32, batch=B, heads=H, L=L, head_dim=hd, scale=scale)
                 ops.round_f16(o32, o_b)
-            ops.gemm_f16(o_b, w["wo"], h2, M, E, E, bias=att.final_linear.bias.data, resid=h)
+            ops.gemm_f16(o_b, w["wo"], h2, M, E, E, bias=att.final_linear.bias.data, resid=h, block_m=bm(E, E))
             if pre:                                                   # layers/transformer.py:63-73
                 ops.layernorm_fwd_f16(h2, ln2.gamma.data, ln2.beta.data, rows=M, D=E, eps=ln2.eps, mode=1, out_plane=t_b)
-                ops.gemm_f16(t_b, w["w1"], None, M, F, E, bias=ffn.linear_1.bias.data, act=1, out_plane=ff_b)
-                ops.gemm_f16(ff_b, w["w2"], h, M, E, F, bias=ffn.linear_2.bias.data, resid=h2)
+                ops.gemm_f16(t_b, w["w1"], None, M, F, E, bias=ffn.linear_1.bias.data, act=1, out_plane=ff_b, block_m=bm(F, E))
+                ops.gemm_f16(ff_b, w["w2"], h, M, E, F, bias=ffn.linear_2.bias.data, resid=h2, block_m=bm(E, F))
             else:                                                     # layers/transformer.py:54-61
                 xn = ws.mat("bf16_xn", M, E)
                 ops.layernorm_fwd_f16(h2, ln1.gamma.data, ln1.beta.data, rows=M, D=E, eps=ln1.eps, mode=1, out=xn, out_plane=t_b)
-                ops.gemm_f16(t_b, w["w1"], None, M, F, E, bias=ffn.linear_1.bias.data, act=1, out_plane=ff_b)
-                ops.gemm_f16(ff_b, w["w2"], h2, M, E, F, bias=ffn.linear_2.bias.data, resid=xn)
+                ops.gemm_f16(t_b, w["w1"], None, M, F, E, bias=ffn.linear_1.bias.data, act=1, out_plane=ff_b, block_m=bm(F, E))
+                ops.gemm_f16(ff_b, w["w2"], h2, M, E, F, bias=ffn.linear_2.bias.data, resid=xn, block_m=bm(E, F))
                 ops.layernorm_fwd_f16(h2, ln2.gamma.data, ln2.beta.data, rows=M, D=E, eps=ln2.eps, mode=1, out=h, out_plane=x_b)
         out = torch.empty(B, L, E, device=dev)
         if self.final_layernorm:

@@ -114,6 +114,9 @@ def parse_args(argv=None):
     ap.add_argument("--f16-attention-long", action="store_true",
                     help="--ppo-shapes --precision f16 (inference): sequences longer than 288 on the key-blocked single-plane f16 "
                          "attention (TransformerEncoder.f16_attention_long) instead of the 3-pass kernels")
+    ap.add_argument("--f16-force-256", action="store_true",
+                    help="--ppo-shapes --precision f16 (inference): every product on the 256 x 256 f16 kernel (ops.f16_force_256: the "
+                         "schedule before the short f16 tiles) -- the other side of an A/B against ops.f16_block_m's dispatch")
     ap.add_argument("--text-seq", type=int, default=196, help="sequence length of the text tower (at most 514)")
     ap.add_argument("--only", choices=("both", "image", "text"), default="both", help="run one tower alone")
     a = ap.parse_args(argv)
@@ -126,6 +129,8 @@ def parse_args(argv=None):
                  "(--precision f16 has --f16-attention-long)")
     if a.f16_attention_long and (a.train or not a.ppo_shapes or a.precision != "f16"):
         ap.error("--f16-attention-long is a switch of the f16 inference mode: give --ppo-shapes --precision f16, not --train")
+    if a.f16_force_256 and (a.train or not a.ppo_shapes or a.precision != "f16"):
+        ap.error("--f16-force-256 is a switch of the f16 inference mode: give --ppo-shapes --precision f16, not --train")
     if (a.text_seq != 196 or a.only != "both") and a.ppo_shapes and not a.train and a.precision not in ("bf16", "f16", "mxfp8"):
         ap.error("--text-seq / --only are switches of the per-tower loop: not of --ppo-shapes without --train "
                  "(--precision bf16 | f16 | mxfp8 excepted: they then run the per-tower loop on their own schedule)")
@@ -142,6 +147,13 @@ def parse_args(argv=None):
 
 def main():
     a = parse_args()
+    if a.f16_force_256:
+        with ops.f16_force_256():
+            return _run(a)
+    return _run(a)
+
+
+def _run(a):
     dev = torch.device("cuda:0")
     ops.set_gemm_passes(a.passes)
     torch.manual_seed(0)

@@ -2,7 +2,9 @@
 """Micro-benchmark of lr2_gemm on the shapes of the LR2PPO head (run on the GPU box).
 usage: python tools/gemm_bench.py [--passes 3] [--iters 20]
        python tools/gemm_bench.py --bf16 [--bm 256|128] [--only ...]: the single-pass bf16 product (lr2_gemm_bf16) on the NT shapes
-       python tools/gemm_bench.py --f16 [--only ...]: the single-pass f16 product (lr2_gemm_f16: the 256 x 256 kernel at every size)
+       python tools/gemm_bench.py --f16 [--bm 256|128|64] [--only ...]: the single-pass f16 product (lr2_gemm_f16_tiled) on the NT shapes;
+           --bm 256: the 256 x 256 kernel under the row split, 128 / 64: the f16 short tiles; without --bm: ops.f16_block_m's choice;
+           --f16-unsplit: lr2_gemm_f16 itself (one launch of the 256 x 256 kernel whatever the size: the baseline of the dispatch)
        python tools/gemm_bench.py --bf16 --tn [--bm 256|128] [--splits S] [--only ...]: the single-pass weight gradient
            (lr2_gemm_bf16_train, TN) on TN_B1_SHAPES, bias gradient included; without --bm each shape is timed on the 256 x 256 TN
            kernel, on the 128-row family at passes = 1 and on the 3-pass 256 x 256 TN kernel, in that order"""
@@ -88,7 +90,7 @@ def bench_tn_b1(a, dev, g):
         del A, B, Ap, Bp, out
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--passes", type=int, default=3)
     ap.add_argument("--iters", type=int, default=20)
@@ -98,14 +100,31 @@ def main():
     ap.add_argument("--splits", type=int, default=None, help="override split-K factor")
     ap.add_argument("--bf16", action="store_true", help="ONE bf16 plane per operand, one pass (ops.gemm_bf16; NT shapes only); "
                     "--bm 256: the 256 x 256 single-pass kernel, --bm 128: the 128-row family at passes = 1; default: by size")
-    ap.add_argument("--f16", action="store_true", help="ONE f16 plane per operand, one pass (ops.gemm_f16; NT shapes only): the "
-                    "256 x 256 kernel at every size (--bm is ignored)")
+    ap.add_argument("--f16", action="store_true", help="ONE f16 plane per operand, one pass (ops.gemm_f16; NT shapes only); "
+                    "--bm 256: the 256 x 256 kernel under the row split, --bm 128 / 64: the f16 kernels of the 128- / 64-row family; "
+                    "default: by size (ops.f16_block_m)")
+    ap.add_argument("--f16-unsplit", action="store_true", help="with --f16: ops.gemm_f16(block_m=None) = lr2_gemm_f16, ONE launch of the "
+                    "256 x 256 kernel at every size, no row split (excludes --bm)")
+    ap.add_argument("--f16-schedule-epilogues", action="store_true", help="with --f16: each product with the epilogue and destination "
+                    "TransformerEncoder.forward_f16 gives it -- N = 4 K (FFN-1): bias, GELU -> ONE f16 plane; N = 3 K (QKV): bias -> ONE "
+                    "f16 plane; otherwise (wo, FFN-2): bias + residual -> fp32 -- instead of a bare fp32 result")
     ap.add_argument("--tn", action="store_true", help="with --bf16: the single-pass weight gradient (ops.gemm_bf16_train, TN) on TN_B1_SHAPES")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     if a.f16 and (a.bf16 or a.tn):
         ap.error("--f16 is a mode of its own: it excludes --bf16 and --tn")
+    if a.f16 and a.bm not in (None, 256, 128, 64):
+        ap.error("--f16 --bm takes 256, 128 or 64")
+    if a.f16_schedule_epilogues and not a.f16:
+        ap.error("--f16-schedule-epilogues is a switch of --f16")
+    if a.f16_unsplit and (not a.f16 or a.bm is not None):
+        ap.error("--f16-unsplit is a switch of --f16 and excludes --bm")
     if a.tn and not a.bf16:
         ap.error("--tn is the weight-gradient form of the single-pass product: give --bf16")
+    return a
+
+
+def main():
+    a = parse_args()
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(0)
     if a.tn:
@@ -120,8 +139,19 @@ def main():
             A = torch.randn(M, K, device=dev, generator=g).to(torch.float16)
             B = torch.randn(N, K, device=dev, generator=g).to(torch.float16)
             out = torch.empty(M, N, device=dev)
-            ms = _time(lambda: ops.gemm_f16(A, B, out, M, N, K), a.iters)
-            print(f"f16x1 NT M={M:6d} N={N:6d} K={K:6d} bm=256: {ms:8.4f} ms  {2.0 * M * N * K / ms / 1e9:7.1f} TFLOP/s", flush=True)
+            bm = None if a.f16_unsplit else (a.bm or ops.f16_block_m(M, N, K))
+            kw, dst, epi = {}, out, "fp32"
+            if a.f16_schedule_epilogues:
+                kw["bias"] = torch.randn(N, device=dev, generator=g)
+                if N in (3 * K, 4 * K):
+                    epi = "bias+gelu->plane" if N == 4 * K else "bias->plane"
+                    kw.update(act=1 if N == 4 * K else 0, out_plane=torch.empty(M * N, dtype=torch.float16, device=dev))
+                    dst = None
+                else:
+                    epi = "bias+resid->fp32"
+                    kw["resid"] = torch.randn(M, N, device=dev, generator=g)
+            ms = _time(lambda: ops.gemm_f16(A, B, dst, M, N, K, block_m=bm, **kw), a.iters)
+            print(f"f16x1 NT M={M:6d} N={N:6d} K={K:6d} {epi} bm={bm or 'unsplit'}: {ms:8.4f} ms  {2.0 * M * N * K / ms / 1e9:7.1f} TFLOP/s", flush=True)
             del A, B, out
             continue
         if a.bf16:
