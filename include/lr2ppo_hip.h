@@ -606,7 +606,7 @@ int lr2_layernorm_fwd_f16(const void* x, const void* gamma, const void* beta, vo
  * first-layer operand, the context of its fallback attention.  n % 4 == 0; src 16-byte, dst 8-byte aligned (else LR2_ERR_SHAPE).
  * replaces: the .half() casts of the 16-bit configuration (BASELINE.json configs[2]; tencentpretrain/utils/ has no kernel of its own). */
 int lr2_round_f16(const void* src, void* dst, uint64_t n, void* stream);
-/* lr2_self_attn_fwd_bf16 on f16 planes (csrc/selfattn_f16.hip): q / k / v ONE f16 plane each (row stride ld elements; the three column
+/* lr2_self_attn_fwd_bf16 on f16 planes (csrc/selfattn_mx.hip): q / k / v ONE f16 plane each (row stride ld elements; the three column
  * blocks of the [rows, 3E] plane lr2_gemm_f16 writes), S and O on the f16 MFMA, fp32 softmax with the row sum of the unrounded
  * probabilities, the un-normalised probabilities rounded to f16 as the A operand of P V, key mask -10000 * (seg <= 0) after the scale;
  * the context rows leave as fp32 (o_f32 [batch * L, ld_o]) and / or as ONE f16 plane (o_f16 [batch * L, ld_o]: the A operand of
@@ -620,7 +620,7 @@ int lr2_self_attn_fwd_f16(const void* q, const void* k, const void* v, int ld, c
  * replaces: nothing (a test hook, as lr2_self_attn_fwd_bf16_blocked_launch_count: which attention a schedule ran). */
 int lr2_self_attn_fwd_f16_launch_count(uint64_t* count);
 /* Added within ABI 27 (purely additive: no signature or struct changes).  lr2_self_attn_fwd_f16 for sequences longer than one
- * LDS-resident head (FeatureExtractor(precision="f16", f16_attention_long=True); csrc/selfattn_f16_blocked.hip): that call's
+ * LDS-resident head (FeatureExtractor(precision="f16", f16_attention_long=True); csrc/selfattn_mx_blocked.hip): that call's
  * argument list, layout, key mask and two outputs -- q / k / v ONE f16 plane each (row stride ld), the context rows out as fp32 (o_f32
  * [batch * L, ld_o]) and / or as ONE f16 plane (o_f16 [batch * L, ld_o]: clamp to +-65504, round to nearest even of the fp32 context);
  * any non-empty subset -- with the keys walked in blocks through LDS by lr2_self_attn_fwd_bf16_blocked's loop on the f16 MFMA:

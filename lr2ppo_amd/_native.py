@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 LIB_PATH = os.path.join(CSRC, "liblr2ppo_hip.so")
-SOURCES = ["gemm.hip", "gemm256.hip", "gemm256_mx.hip", "gemm256_b1.hip", "gemm256_f16.hip", "gemm256_tn_b1.hip", "norm.hip", "attn.hip", "selfattn_fwd.hip", "selfattn_bwd.hip", "first_token_attn.hip", "selfattn_mx.hip", "selfattn_f16.hip", "selfattn_mx_blocked.hip", "selfattn_f16_blocked.hip", "selfattn_b1_train.hip", "selfattn_b1_blocked.hip", "misc.hip", "fp8.hip", "fp8_train.hip"]
+SOURCES = ["gemm.hip", "gemm256.hip", "gemm256_mx.hip", "gemm256_b1.hip", "gemm256_f16.hip", "gemm256_tn_b1.hip", "norm.hip", "attn.hip", "selfattn_fwd.hip", "selfattn_bwd.hip", "first_token_attn.hip", "selfattn_mx.hip", "selfattn_mx_blocked.hip","selfattn_b1_train.hip", "selfattn_b1_blocked.hip", "misc.hip", "fp8.hip", "fp8_train.hip"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "gemm256_ring.h"), os.path.join(CSRC, "fp8_common.h"), os.path.join(CSRC, "selfattn_common.h"), os.path.join(CSRC, "selfattn_b1.h"), os.path.join(INCLUDE, "lr2ppo_hip.h")]
 
 ABI_VERSION = 27     # == LR2_ABI_VERSION of include/lr2ppo_hip.h (tests assert the two agree)

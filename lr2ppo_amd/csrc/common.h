@@ -128,6 +128,33 @@ __device__ __forceinline__ float group8_max(float v) {
   return fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true)));
 }
 
+// ---- the MX-FP8 block rule (OCP MX v1.0 section 6.3; 32 elements share one E8M0 scale), stated once for every kernel that quantises ----
+// shared exponent floor(log2(amax)) - emax(e4m3 = 8) in [-127, 127]; amax = 0 (or denormal): the smallest scale.  The scale byte is e + 127.
+__device__ __forceinline__ int mx_exponent(float amax) {
+  int e = (int)((__float_as_uint(amax) >> 23) & 0xFF) - 127 - 8;
+  if (amax < 1.17549435e-38f) e = -127;
+  if (e < -127) e = -127;
+  if (e > 127) e = 127;
+  return e;
+}
+__device__ __forceinline__ float mx_inverse(int e) {
+  const uint32_t ef = (uint32_t)(127 - e);
+  return __uint_as_float(ef ? ef << 23 : 0x00400000u);       // 2^-e (e = 127: the denormal 2^-127)
+}
+// four values -> four e4m3fn bytes (saturating at +-448, round to nearest even) in one word, element order = argument order
+__device__ __forceinline__ int mx_pack4(float a, float b, float c, float d, float inv) {
+  int w = 0;
+  w = __builtin_amdgcn_cvt_pk_fp8_f32(__builtin_amdgcn_fmed3f(a * inv, -448.f, 448.f), __builtin_amdgcn_fmed3f(b * inv, -448.f, 448.f), w, false);
+  w = __builtin_amdgcn_cvt_pk_fp8_f32(__builtin_amdgcn_fmed3f(c * inv, -448.f, 448.f), __builtin_amdgcn_fmed3f(d * inv, -448.f, 448.f), w, true);
+  return w;
+}
+// the common shape: 4 consecutive columns of a row whose 32-column block is 8 consecutive lanes -> the packed word; e = the block's exponent
+__device__ __forceinline__ int mx_quant4_group8(float4 v, int& e) {
+  const float amax = group8_max(fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
+  e = mx_exponent(amax);
+  return mx_pack4(v.x, v.y, v.z, v.w, mx_inverse(e));
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -34,20 +34,10 @@ __global__ __launch_bounds__(256) void quant_mxfp8_kernel(const float* __restric
     float amax = fmaxf(fmaxf(fmaxf(fabsf(a.x), fabsf(a.y)), fmaxf(fabsf(a.z), fabsf(a.w))),
                        fmaxf(fmaxf(fabsf(b.x), fabsf(b.y)), fmaxf(fabsf(b.z), fabsf(b.w))));
     amax = group4_max(amax);         // the block's 32 elements = 4 consecutive lanes (k8 is a multiple of 4)
-    // shared exponent: floor(log2(amax)) - emax(e4m3 = 8), as a biased E8M0 byte; amax = 0 (or denormal): the smallest scale
-    const int ex = (int)((__float_as_uint(amax) >> 23) & 0xFF) - 127;          // floor(log2(amax)) of a normal float
-    int e = ex - 8;
-    if (amax < 1.17549435e-38f) e = -127;
-    if (e < -127) e = -127;
-    if (e > 127) e = 127;
-    const uint32_t ef = (uint32_t)(127 - e);
-    const float inv = __uint_as_float(ef ? ef << 23 : 0x00400000u);       // 2^-e (e = 127: the denormal 2^-127)
-    auto sat = [](float v) { return __builtin_amdgcn_fmed3f(v, -448.0f, 448.0f); };
-    int w0 = 0, w1 = 0;
-    w0 = __builtin_amdgcn_cvt_pk_fp8_f32(sat(a.x * inv), sat(a.y * inv), w0, false);
-    w0 = __builtin_amdgcn_cvt_pk_fp8_f32(sat(a.z * inv), sat(a.w * inv), w0, true);
-    w1 = __builtin_amdgcn_cvt_pk_fp8_f32(sat(b.x * inv), sat(b.y * inv), w1, false);
-    w1 = __builtin_amdgcn_cvt_pk_fp8_f32(sat(b.z * inv), sat(b.w * inv), w1, true);
+    // common.h's block rule: the shared exponent as a biased E8M0 byte, the elements scaled by 2^-e
+    const int e = mx_exponent(amax);
+    const float inv = mx_inverse(e);
+    const int w0 = mx_pack4(a.x, a.y, a.z, a.w, inv), w1 = mx_pack4(b.x, b.y, b.z, b.w, inv);
     if (ok) {
       *reinterpret_cast<int2*>(q + (size_t)r * K + 8 * g) = make_int2(w0, w1);
       if ((g & 3) == 0) s[(size_t)r * (K / 32) + (g >> 2)] = (uint8_t)(e + 127);
@@ -208,17 +198,8 @@ __global__ __launch_bounds__(256, 2) void gemm_mxfp8_lds_kernel(Mx8Params p) {
           const float4 rr = *reinterpret_cast<const float4*>(p.resid + (size_t)m * p.ld_resid + n);
           v.x += rr.x; v.y += rr.y; v.z += rr.z; v.w += rr.w;
         }
-        float amax = fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
-        amax = group8_max(amax);
-        int e = (int)((__float_as_uint(amax) >> 23) & 0xFF) - 127 - 8;
-        if (amax < 1.17549435e-38f) e = -127;
-        if (e < -127) e = -127;
-        if (e > 127) e = 127;
-        const uint32_t ef = (uint32_t)(127 - e);
-        const float inv = __uint_as_float(ef ? ef << 23 : 0x00400000u);
-        int w = 0;
-        w = __builtin_amdgcn_cvt_pk_fp8_f32(__builtin_amdgcn_fmed3f(v.x * inv, -448.f, 448.f), __builtin_amdgcn_fmed3f(v.y * inv, -448.f, 448.f), w, false);
-        w = __builtin_amdgcn_cvt_pk_fp8_f32(__builtin_amdgcn_fmed3f(v.z * inv, -448.f, 448.f), __builtin_amdgcn_fmed3f(v.w * inv, -448.f, 448.f), w, true);
+        int e;
+        const int w = mx_quant4_group8(v, e);
         if (m < p.M) {
           *reinterpret_cast<int*>(p.out_q + (size_t)m * p.N + n) = w;
           if ((lane & 7) == 0) p.out_s[(size_t)m * (p.N / 32) + (n >> 5)] = (uint8_t)(e + 127);

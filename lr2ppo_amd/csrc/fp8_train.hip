@@ -10,29 +10,10 @@
 
 namespace {
 
-// the scale rule of quant_mxfp8_kernel (fp8.hip): shared exponent floor(log2(amax)) - 8 in [-127, 127], -127 below FLT_MIN
-__device__ __forceinline__ int mx_exponent(float amax) {
-  int e = (int)((__float_as_uint(amax) >> 23) & 0xFF) - 127 - 8;
-  if (amax < 1.17549435e-38f) e = -127;
-  if (e < -127) e = -127;
-  if (e > 127) e = 127;
-  return e;
-}
-__device__ __forceinline__ float mx_inverse(int e) {
-  const uint32_t ef = (uint32_t)(127 - e);
-  return __uint_as_float(ef ? ef << 23 : 0x00400000u);       // 2^-e (e = 127: the denormal 2^-127)
-}
-// 32 values -> 32 e4m3fn bytes (saturating, round to nearest even), four per word in element order
+// 32 values -> 32 e4m3fn bytes by common.h's block rule, four per word in element order
 __device__ __forceinline__ void mx_pack32(const float (&v)[32], float inv, int (&w)[8]) {
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    int x = 0;
-    x = __builtin_amdgcn_cvt_pk_fp8_f32(__builtin_amdgcn_fmed3f(v[4 * j] * inv, -448.f, 448.f),
-                                        __builtin_amdgcn_fmed3f(v[4 * j + 1] * inv, -448.f, 448.f), x, false);
-    x = __builtin_amdgcn_cvt_pk_fp8_f32(__builtin_amdgcn_fmed3f(v[4 * j + 2] * inv, -448.f, 448.f),
-                                        __builtin_amdgcn_fmed3f(v[4 * j + 3] * inv, -448.f, 448.f), x, true);
-    w[j] = x;
-  }
+  for (int j = 0; j < 8; ++j) w[j] = mx_pack4(v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3], inv);
 }
 
 struct QuantTParams {

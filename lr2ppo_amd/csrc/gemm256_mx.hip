@@ -199,17 +199,8 @@ __device__ __forceinline__ float4 mx_finish(const Mx8Params& p, float4 v, float4
 }
 // the row's 32-column MX block = 8 consecutive lanes x 4 columns: quantise as lr2_quant_mxfp8 would the stored row
 __device__ __forceinline__ void mx_quant_store(const Mx8Params& p, float4 v, int m, int n, int lane, bool ok) {
-  float amax = fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
-  amax = group8_max(amax);
-  int e = (int)((__float_as_uint(amax) >> 23) & 0xFF) - 127 - 8;
-  if (amax < 1.17549435e-38f) e = -127;
-  if (e < -127) e = -127;
-  if (e > 127) e = 127;
-  const uint32_t ef = (uint32_t)(127 - e);
-  const float inv = __uint_as_float(ef ? ef << 23 : 0x00400000u);
-  int w = 0;
-  w = __builtin_amdgcn_cvt_pk_fp8_f32(__builtin_amdgcn_fmed3f(v.x * inv, -448.f, 448.f), __builtin_amdgcn_fmed3f(v.y * inv, -448.f, 448.f), w, false);
-  w = __builtin_amdgcn_cvt_pk_fp8_f32(__builtin_amdgcn_fmed3f(v.z * inv, -448.f, 448.f), __builtin_amdgcn_fmed3f(v.w * inv, -448.f, 448.f), w, true);
+  int e;
+  const int w = mx_quant4_group8(v, e);
   if (ok) {
     *reinterpret_cast<int*>(p.out_q + (size_t)m * p.N + n) = w;
     if ((lane & 7) == 0) p.out_s[(size_t)m * (p.N / 32) + (n >> 5)] = (uint8_t)(e + 127);

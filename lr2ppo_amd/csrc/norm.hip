@@ -70,19 +70,10 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
         else store_bf16x4(out_hi + off + e, y);
       }
       if (out_q) {
-        // MX-FP8 (csrc/fp8.hip's rule): a 32-column block = 8 consecutive lanes x 4 columns; D % 32 == 0, so a block's lanes are
+        // MX-FP8 (common.h's block rule): a 32-column block = 8 consecutive lanes x 4 columns; D % 32 == 0, so a block's lanes are
         // all inside the row or all outside
-        float amax = fmaxf(fmaxf(fabsf(y.x), fabsf(y.y)), fmaxf(fabsf(y.z), fabsf(y.w)));
-        amax = group8_max(amax);
-        int ex = (int)((__float_as_uint(amax) >> 23) & 0xFF) - 127 - 8;
-        if (amax < 1.17549435e-38f) ex = -127;
-        if (ex < -127) ex = -127;
-        if (ex > 127) ex = 127;
-        const uint32_t ef = (uint32_t)(127 - ex);
-        const float inv = __uint_as_float(ef ? ef << 23 : 0x00400000u);
-        int w = 0;
-        w = __builtin_amdgcn_cvt_pk_fp8_f32(__builtin_amdgcn_fmed3f(y.x * inv, -448.f, 448.f), __builtin_amdgcn_fmed3f(y.y * inv, -448.f, 448.f), w, false);
-        w = __builtin_amdgcn_cvt_pk_fp8_f32(__builtin_amdgcn_fmed3f(y.z * inv, -448.f, 448.f), __builtin_amdgcn_fmed3f(y.w * inv, -448.f, 448.f), w, true);
+        int ex;
+        const int w = mx_quant4_group8(y, ex);
         *reinterpret_cast<int*>(out_q + (size_t)r * D + e) = w;
         if ((lane & 7) == 0) out_s[(size_t)r * (D / 32) + (e >> 5)] = (uint8_t)(ex + 127);
       }

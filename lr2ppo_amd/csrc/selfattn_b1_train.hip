@@ -9,7 +9,7 @@
 // Structure: the simple one-workgroup-per-(sequence, head) form only -- 8 waves, the head's resident operands (K, V / Q, dO: L <= 288
 // rows, one plane each, 72 KiB at most) in LDS, each wave walks over 16-row sub-tiles; small batches split the sub-tiles over up to
 // 4 workgroups (attn_chunks).  No persistent form, no LDS-DMA movers.
-//   * forward  = self_attn_bf16_mx_kernel's arithmetic (selfattn_mx.hip), instruction for instruction, + the dropout factor on the
+//   * forward  = self_attn_plane_kernel<false, ..>'s arithmetic (selfattn_mx.hip), instruction for instruction, + the dropout factor on the
 //     un-normalised probabilities before they are rounded to the A fragment of P V + lse: at drop_p = 0 the same bytes;
 //   * backward = self_attn_bwd_dq_kernel / self_attn_bwd_dkv_kernel's one-block recomputing form (selfattn_bwd.hip) with one plane
 //     where those stage two and one MFMA where they call mfma3; dS, Pd = P o M and the three outputs are rounded to bf16 (RNE).
@@ -19,7 +19,7 @@
 
 namespace {
 
-// ---- forward: self_attn_bf16_mx_kernel with dropout on the probabilities and the log-sum-exp ----
+// ---- forward: self_attn_plane_kernel<false, ..> with dropout on the probabilities and the log-sum-exp ----
 template <int NT, int NW>
 __global__ __launch_bounds__(64 * NW) void self_attn_b1_train_fwd_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
                                                                          const bf16_t* __restrict__ V, int ld,

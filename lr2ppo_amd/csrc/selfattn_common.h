@@ -1,6 +1,6 @@
 // What the self-attention sources share -- selfattn_fwd.hip (one-block, persistent and key-blocked forwards), selfattn_bwd.hip (recomputing
-// and streaming persistent backwards), selfattn_mx.hip (the MX-FP8 mode's single-plane forward) and first_token_attn.hip (HD only): the
-// constants and the probability dropout, the LDS images of a head's rows, the movers HBM -> LDS, MFMA fragment loads and tile stores, and
+// and streaming persistent backwards), selfattn_mx.hip / selfattn_mx_blocked.hip (the single-plane inference forwards, bf16 and f16)
+// and first_token_attn.hip (HD only): the constants and the probability dropout, the LDS images of a head's rows, the movers HBM -> LDS, MFMA fragment loads and tile stores, and
 // the host-side pieces of the launchers (CU count, descriptor spans, the "does this shape take the persistent form" predicates), once.
 //
 // Left alone, on purpose:
@@ -125,7 +125,7 @@ __device__ __forceinline__ bf16x8_t tr_pair_k(const char* plane, int row_a, int 
 }
 
 // ---- the persistent forms: one workgroup per CU walks over (sequence, head) pairs, the resident planes travel by LDS-DMA under the
-// compute (self_attn_persist_kernel, self_attn_bwd_{dq,dkv}_persist_kernel, self_attn_bf16_mx_persist_kernel) ----
+// compute (self_attn_persist_kernel, self_attn_bwd_{dq,dkv}_persist_kernel, self_attn_plane_persist_kernel) ----
 // A one-pair forward spends a quarter of its time waiting for its K / V planes (112 KiB per workgroup, one workgroup per CU: nothing
 // else runs meanwhile), every workgroup pays its launch and the drain of its last stores, and its phases (staging, S, softmax, P V,
 // stores) barely overlap: two waves per SIMD in the same phase (measured by ablation, profiles/experiments/README.md).  In a persistent
@@ -231,6 +231,39 @@ __device__ __forceinline__ f32x4_t mfma3(bf16x8_t ah, bf16x8_t al, bf16x8_t bh, 
   acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, acc, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, acc, 0, 0, 0);
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, acc, 0, 0, 0);
+}
+
+// ---- the two operand formats of the single-plane inference kernels (selfattn_mx.hip, selfattn_mx_blocked.hip) ----
+// F16 is a compile-time parameter of those kernels: false = bf16 planes (the "bf16" and MX-FP8 modes), true = IEEE f16 planes (the "f16"
+// mode: 11 significand bits, three more).  The f16 MFMA has the bf16 one's operand bytes and fragment layout, so the staging, the
+// ds_read_b128 / ds_read_b64_tr_b16 fragment reads and the 16-byte fragment type (bf16x8_t then means "16 raw bytes") are shared.  The
+// format selects the three helpers below, whether the MX-FP8 outputs exist (bf16 only), and one sched_barrier of mx_phase_a -- no more.
+__device__ __forceinline__ f32x4_t mfma_f16(bf16x8_t a, bf16x8_t b, f32x4_t c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
+}
+// two probabilities -> packed f16 pair (low half = a), one v_cvt_pk_f16_f32.  Un-normalised probabilities are in (0, 1]: no clamp needed;
+// below 2^-14 they are f16 subnormals, below 2^-25 zero -- an absolute error of at most 2^-25 against a row sum >= 1, which is formed in
+// fp32 from the unrounded values in both formats
+__device__ __forceinline__ uint32_t prob_pk_f16(float a, float b) {
+  f32x2_t v = {a, b};
+  f16x2_t r = __builtin_convertvector(v, f16x2_t);
+  return __builtin_bit_cast(uint32_t, r);
+}
+template <bool F16>
+__device__ __forceinline__ f32x4_t mfma_plane(bf16x8_t a, bf16x8_t b, f32x4_t c) {
+  if constexpr (F16) return mfma_f16(a, b, c);
+  else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+}
+template <bool F16>
+__device__ __forceinline__ uint32_t prob_pk(float a, float b) {
+  if constexpr (F16) return prob_pk_f16(a, b);
+  else return cvt_pk_bf16(a, b);
+}
+// four context values -> ONE plane: round to nearest even (f16: common.h's writer, clamped to +-65504)
+template <bool F16>
+__device__ __forceinline__ void store_plane4(bf16_t* p, float4 v) {
+  if constexpr (F16) store_f16x4(p, v);
+  else store_bf16x4(p, v);
 }
 
 // 16 x 64 accumulator tile (o[n][r] = X[row 4g + r][col 16n + (l & 15)]) -> planes rows via the wave's LDS slab

@@ -12,17 +12,23 @@
 // fragments, V for ds_read_b64_tr_b16); each wave walks over 16-query sub-tiles: S^T = K Q^T (2 MFMAs per 16 keys), softmax in the
 // log2 domain across the 4 lanes that share a query, P as bf16 straight from the accumulators, O = P V (4 MFMAs per 32 keys),
 // 1 / sum on the 16 outputs, rows through the wave's LDS slab -> fp32 and / or MX-FP8.
+//
+// The same two kernels serve the f16 inference mode (FeatureExtractor(precision="f16"); lr2_self_attn_fwd_f16 below): Q, K, V as ONE f16
+// plane each (what lr2_gemm_f16 writes with out_lo_off = 0), the context as fp32 and / or ONE f16 plane.  The format is the kernels'
+// compile-time parameter F16; what it selects is listed in selfattn_common.h ("the two operand formats").  Both formats take one
+// parameter list -- the f16 instantiations receive null Oq / Os -- so the bf16 instantiations are, instruction for instruction, what
+// they were when this file held them alone (DESIGN.md 4.5 says how that is checked).
 
 #include "selfattn_common.h"
 
 namespace {
 
-template <int NT, int NW>
-__global__ __launch_bounds__(64 * NW) void self_attn_bf16_mx_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
-                                                                    const bf16_t* __restrict__ V, int ld,
-                                                                    const int64_t* __restrict__ seg, float* __restrict__ Of,
-                                                                    uint8_t* __restrict__ Oq, uint8_t* __restrict__ Os,
-                                                                    bf16_t* __restrict__ Ob, int ld_o, int heads, int L, float scale) {
+template <bool F16, int NT, int NW>
+__global__ __launch_bounds__(64 * NW) void self_attn_plane_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
+                                                                  const bf16_t* __restrict__ V, int ld,
+                                                                  const int64_t* __restrict__ seg, float* __restrict__ Of,
+                                                                  uint8_t* __restrict__ Oq, uint8_t* __restrict__ Os,
+                                                                  bf16_t* __restrict__ Ob, int ld_o, int heads, int L, float scale) {
   constexpr int LP = 16 * NT;
   constexpr int PLANE = LP * ROW_B;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -95,7 +101,7 @@ __global__ __launch_bounds__(64 * NW) void self_attn_bf16_mx_kernel(const bf16_t
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
         const bf16x8_t kf = *reinterpret_cast<const bf16x8_t*>(sK + k_off(16 * t + qn, g + 4 * ks));
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, q[ks], acc, 0, 0, 0);
+        acc = mfma_plane<F16>(kf, q[ks], acc);
       }
       s[t] = acc;
     }
@@ -130,14 +136,14 @@ __global__ __launch_bounds__(64 * NW) void self_attn_bf16_mx_kernel(const bf16_t
     const int i16 = lane & 15, tq = i16 >> 2, tp = i16 & 3;
 #pragma unroll
     for (int u = 0; u < NT / 2; ++u) {
-      const u32x4_t pw = {cvt_pk_bf16(s[2 * u][0], s[2 * u][1]), cvt_pk_bf16(s[2 * u][2], s[2 * u][3]),
-                          cvt_pk_bf16(s[2 * u + 1][0], s[2 * u + 1][1]), cvt_pk_bf16(s[2 * u + 1][2], s[2 * u + 1][3])};
+      const u32x4_t pw = {prob_pk<F16>(s[2 * u][0], s[2 * u][1]), prob_pk<F16>(s[2 * u][2], s[2 * u][3]),
+                          prob_pk<F16>(s[2 * u + 1][0], s[2 * u + 1][1]), prob_pk<F16>(s[2 * u + 1][2], s[2 * u + 1][3])};
       const bf16x8_t pf = __builtin_bit_cast(bf16x8_t, pw);
       const int ra = 32 * u + 4 * g + tq, rb = ra + 16;
 #pragma unroll
       for (int n = 0; n < 4; ++n) {
         const bf16x8_t vf = tr_pair(sV, ra, rb, 2 * n + (tp >> 1), 8 * (tp & 1));
-        o[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf, vf, o[n], 0, 0, 0);
+        o[n] = mfma_plane<F16>(pf, vf, o[n]);
       }
     }
     // ---- o[n][r] = O[query 4 g + r][hd 16 n + (l & 15)] -> slab -> row-contiguous fp32 / MX-FP8 ----
@@ -157,20 +163,11 @@ __global__ __launch_bounds__(64 * NW) void self_attn_bf16_mx_kernel(const bf16_t
       const float4 v = *reinterpret_cast<const float4*>(slab + r * (HD + 4) + c);
       const size_t row = row0 + (ok ? qr : 0);
       if (Of && ok) *reinterpret_cast<float4*>(Of + row * (size_t)ld_o + col0 + c) = v;
-      if (Ob && ok) store_bf16x4(Ob + row * (size_t)ld_o + col0 + c, v);       // ONE bf16 plane: RNE of the fp32 context
-      if (Oq) {
+      if (Ob && ok) store_plane4<F16>(Ob + row * (size_t)ld_o + col0 + c, v);   // ONE bf16 / f16 plane: RNE of the fp32 context
+      if (!F16 && Oq) {
         // the row's 32-column MX block = 8 consecutive lanes x 4 columns (the head's 64 columns are two blocks): as lr2_quant_mxfp8
-        float amax = fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
-        amax = group8_max(amax);
-        int e = (int)((__float_as_uint(amax) >> 23) & 0xFF) - 127 - 8;
-        if (amax < 1.17549435e-38f) e = -127;
-        if (e < -127) e = -127;
-        if (e > 127) e = 127;
-        const uint32_t ef = (uint32_t)(127 - e);
-        const float sc = __uint_as_float(ef ? ef << 23 : 0x00400000u);
-        int w = 0;
-        w = __builtin_amdgcn_cvt_pk_fp8_f32(__builtin_amdgcn_fmed3f(v.x * sc, -448.f, 448.f), __builtin_amdgcn_fmed3f(v.y * sc, -448.f, 448.f), w, false);
-        w = __builtin_amdgcn_cvt_pk_fp8_f32(__builtin_amdgcn_fmed3f(v.z * sc, -448.f, 448.f), __builtin_amdgcn_fmed3f(v.w * sc, -448.f, 448.f), w, true);
+        int e;
+        const int w = mx_quant4_group8(v, e);
         if (ok) {
           *reinterpret_cast<int*>(Oq + row * (size_t)ld_o + col0 + c) = w;
           if ((lane & 7) == 0) Os[row * (size_t)(ld_o / 32) + ((col0 + c) >> 5)] = (uint8_t)(e + 127);
@@ -188,7 +185,7 @@ __global__ __launch_bounds__(64 * NW) void self_attn_bf16_mx_kernel(const bf16_t
 // same bits as the one-pair kernel above.
 
 // phase A of one 16-query sub-tile: S^T = K Q^T, softmax in the log2 domain -> un-normalised probabilities as bf16 fragments + 1 / sum
-template <int NT>
+template <bool F16, int NT>
 __device__ __forceinline__ void mx_phase_a(const char* sK, const float* sMask, const bf16x8_t (&q)[2], int lane, float scale2,
                                            bf16x8_t (&pf)[NT / 2], float& inv) {
   const int qn = lane & 15, g = lane >> 4;
@@ -199,9 +196,14 @@ __device__ __forceinline__ void mx_phase_a(const char* sK, const float* sMask, c
     f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_ld16(kb[ks] + 2048 * t), q[ks], acc, 0, 0, 0);
+      acc = mfma_plane<F16>(lds_ld16(kb[ks] + 2048 * t), q[ks], acc);
     }
     s[t] = acc;
+    // f16 only: K fragments are requested at most three tiles (six ds_read_b128) ahead: left free, the scheduler hoists enough of them
+    // that the NT = 14 / 18 instantiations spill 2 / 16 VGPRs at the 168 a 12-wave workgroup has (the bf16 kernel lands just inside them)
+    if constexpr (F16) {
+      if (t % 3 == 2) __builtin_amdgcn_sched_barrier(0);
+    }
   }
   float mx = -INFINITY;
 #pragma unroll
@@ -228,14 +230,14 @@ __device__ __forceinline__ void mx_phase_a(const char* sK, const float* sMask, c
   inv = 1.0f / sum;
 #pragma unroll
   for (int u = 0; u < NT / 2; ++u) {
-    const u32x4_t pw = {cvt_pk_bf16(s[2 * u][0], s[2 * u][1]), cvt_pk_bf16(s[2 * u][2], s[2 * u][3]),
-                        cvt_pk_bf16(s[2 * u + 1][0], s[2 * u + 1][1]), cvt_pk_bf16(s[2 * u + 1][2], s[2 * u + 1][3])};
+    const u32x4_t pw = {prob_pk<F16>(s[2 * u][0], s[2 * u][1]), prob_pk<F16>(s[2 * u][2], s[2 * u][3]),
+                        prob_pk<F16>(s[2 * u + 1][0], s[2 * u + 1][1]), prob_pk<F16>(s[2 * u + 1][2], s[2 * u + 1][3])};
     pf[u] = __builtin_bit_cast(bf16x8_t, pw);
   }
 }
 
 // phase B: O = (P~ V) / sum, rows through the wave's slab -> fp32 and / or MX-FP8 (the one-pair kernel's code)
-template <int NT>
+template <bool F16, int NT>
 __device__ __forceinline__ void mx_phase_b(const char* sV, float* slab, const bf16x8_t (&pf)[NT / 2], float inv, int sub, int lane, int L,
                                            size_t row0, int col0, float* __restrict__ Of, uint8_t* __restrict__ Oq,
                                            uint8_t* __restrict__ Os, bf16_t* __restrict__ Ob, int ld_o) {
@@ -252,7 +254,7 @@ __device__ __forceinline__ void mx_phase_b(const char* sV, float* slab, const bf
 #pragma unroll
     for (int n = 0; n < 4; ++n) {
       const uint32_t a = vb[n] + 4096 * u;
-      o[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf[u], lds_tr_pair(a, a + 2048), o[n], 0, 0, 0);
+      o[n] = mfma_plane<F16>(pf[u], lds_tr_pair(a, a + 2048), o[n]);
     }
   }
   float inv_q[4];
@@ -273,19 +275,10 @@ __device__ __forceinline__ void mx_phase_b(const char* sV, float* slab, const bf
     const uint32_t lrow = (uint32_t)(ok ? qr : 0);
     const size_t ubase = row0 * (size_t)ld_o + col0, sbase = row0 * (size_t)(ld_o / 32) + (col0 >> 5);
     if (Of && ok) *reinterpret_cast<float4*>(Of + ubase + (lrow * (uint32_t)ld_o + (uint32_t)c)) = v;
-    if (Ob && ok) store_bf16x4(Ob + ubase + (lrow * (uint32_t)ld_o + (uint32_t)c), v);
-    if (Oq) {
-      float amax = fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
-      amax = group8_max(amax);
-      int e = (int)((__float_as_uint(amax) >> 23) & 0xFF) - 127 - 8;
-      if (amax < 1.17549435e-38f) e = -127;
-      if (e < -127) e = -127;
-      if (e > 127) e = 127;
-      const uint32_t ef = (uint32_t)(127 - e);
-      const float sc = __uint_as_float(ef ? ef << 23 : 0x00400000u);
-      int w = 0;
-      w = __builtin_amdgcn_cvt_pk_fp8_f32(__builtin_amdgcn_fmed3f(v.x * sc, -448.f, 448.f), __builtin_amdgcn_fmed3f(v.y * sc, -448.f, 448.f), w, false);
-      w = __builtin_amdgcn_cvt_pk_fp8_f32(__builtin_amdgcn_fmed3f(v.z * sc, -448.f, 448.f), __builtin_amdgcn_fmed3f(v.w * sc, -448.f, 448.f), w, true);
+    if (Ob && ok) store_plane4<F16>(Ob + ubase + (lrow * (uint32_t)ld_o + (uint32_t)c), v);
+    if (!F16 && Oq) {
+      int e;
+      const int w = mx_quant4_group8(v, e);
       if (ok) {
         *reinterpret_cast<int*>(Oq + ubase + (lrow * (uint32_t)ld_o + (uint32_t)c)) = w;
         if ((lane & 7) == 0) Os[sbase + (lrow * (uint32_t)(ld_o / 32) + (uint32_t)(c >> 5))] = (uint8_t)(e + 127);
@@ -295,14 +288,13 @@ __device__ __forceinline__ void mx_phase_b(const char* sV, float* slab, const bf
   __builtin_amdgcn_wave_barrier();
 }
 
-template <int NT>
-__global__ __launch_bounds__(64 * PM_WAVES) void self_attn_bf16_mx_persist_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
-                                                                                  const bf16_t* __restrict__ V, int ld,
-                                                                                  const int64_t* __restrict__ seg, float* __restrict__ Of,
-                                                                                  uint8_t* __restrict__ Oq, uint8_t* __restrict__ Os,
-                                                                                  bf16_t* __restrict__ Ob, int ld_o, int heads, int L,
-                                                                                  float scale, int n_pairs,
-                                                                                  uint32_t kv_bytes) {
+template <bool F16, int NT>
+__global__ __launch_bounds__(64 * PM_WAVES) void self_attn_plane_persist_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
+                                                                                const bf16_t* __restrict__ V, int ld,
+                                                                                const int64_t* __restrict__ seg, float* __restrict__ Of,
+                                                                                uint8_t* __restrict__ Oq, uint8_t* __restrict__ Os,
+                                                                                bf16_t* __restrict__ Ob, int ld_o, int heads, int L,
+                                                                                float scale, int n_pairs, uint32_t kv_bytes) {
   constexpr int LP = 16 * NT;
   constexpr int PLANE = LP * ROW_B;
   constexpr int MK = (LP + 64 * PM_MOVERS - 1) / (64 * PM_MOVERS);
@@ -388,48 +380,51 @@ __global__ __launch_bounds__(64 * PM_WAVES) void self_attn_bf16_mx_persist_kerne
     float inv0 = 0.f, inv1 = 0.f;
     bf16x8_t q1[2];
     load_q(row0, col0, sub1, q1);                  // travels under the first sub-tile's phase A
-    if (has0) mx_phase_a<NT>(sK, mask, q0, opaque(lane), scale2, p0, inv0);
-    if (has1) mx_phase_a<NT>(sK, mask, q1, opaque(lane), scale2, p1, inv1);
+    if (has0) mx_phase_a<F16, NT>(sK, mask, q0, opaque(lane), scale2, p0, inv0);
+    if (has1) mx_phase_a<F16, NT>(sK, mask, q1, opaque(lane), scale2, p1, inv1);
     phase_barrier();
     const int pn = p + gridDim.x;
     const bool more = pn < n_pairs;
     const int bn = __builtin_amdgcn_readfirstlane(pn / heads), hn = pn - bn * heads;
     const size_t row0n = (size_t)bn * L;
-    if (has0) mx_phase_b<NT>(sV, slab, p0, inv0, sub0, opaque(lane), L, row0, col0, Of, Oq, Os, Ob, ld_o);
+    if (has0) mx_phase_b<F16, NT>(sV, slab, p0, inv0, sub0, opaque(lane), L, row0, col0, Of, Oq, Os, Ob, ld_o);
     if (more) load_q(row0n, hn * HD, sub0, q0);    // the next pair's first sub-tile: under the second sub-tile's P V
-    if (has1) mx_phase_b<NT>(sV, slab, p1, inv1, sub1, opaque(lane), L, row0, col0, Of, Oq, Os, Ob, ld_o);
+    if (has1) mx_phase_b<F16, NT>(sV, slab, p1, inv1, sub1, opaque(lane), L, row0, col0, Of, Oq, Os, Ob, ld_o);
     if (!more) break;
     phase_barrier();
     p = pn; row0 = row0n; col0 = hn * HD;
   }
 }
 
-template <int NT>
+template <bool F16, int NT>
 int launch_persist(const bf16_t* q, const bf16_t* k, const bf16_t* v, int ld, const int64_t* seg, float* of, uint8_t* oq, uint8_t* os,
                    bf16_t* ob, int ld_o, int batch, int heads, int L, float scale, hipStream_t stream) {
   constexpr int LP = 16 * NT;
   const size_t lds = (size_t)2 * LP * ROW_B + (size_t)2 * LP * 4 + (size_t)PM_COMPUTE * 16 * (HD + 4) * 4;
   static bool done = false;
-  if (allow_lds_once(self_attn_bf16_mx_persist_kernel<NT>, lds, done, "self_attn_fwd_bf16(persistent)")) return LR2_ERR_LAUNCH;
+  if (allow_lds_once(self_attn_plane_persist_kernel<F16, NT>, lds, done, F16 ? "self_attn_fwd_f16(persistent)" : "self_attn_fwd_bf16(persistent)"))
+    return LR2_ERR_LAUNCH;
   const int n_pairs = batch * heads;
-  LR2_LAUNCH((self_attn_bf16_mx_persist_kernel<NT>), dim3(persist_grid(n_pairs)), dim3(64 * PM_WAVES), lds, stream, q, k, v, ld, seg, of,
+  LR2_LAUNCH((self_attn_plane_persist_kernel<F16, NT>), dim3(persist_grid(n_pairs)), dim3(64 * PM_WAVES), lds, stream, q, k, v, ld, seg, of,
              oq, os, ob, ld_o, heads, L, scale, n_pairs, (uint32_t)operand_span_bytes(batch, L, ld, heads));
-  return lr2_launch_status("lr2_self_attn_fwd_bf16(persistent)");
+  return lr2_launch_status(F16 ? "lr2_self_attn_fwd_f16(persistent)" : "lr2_self_attn_fwd_bf16(persistent)");
 }
 
-template <int NT>
+template <bool F16, int NT>
 int launch(const bf16_t* q, const bf16_t* k, const bf16_t* v, int ld, const int64_t* seg, float* of, uint8_t* oq, uint8_t* os, bf16_t* ob,
            int ld_o, int batch, int heads, int L, float scale, hipStream_t stream) {
   if (bf16_persist_ok(batch, heads, L, ld))
-    return launch_persist<NT>(q, k, v, ld, seg, of, oq, os, ob, ld_o, batch, heads, L, scale, stream);
+    return launch_persist<F16, NT>(q, k, v, ld, seg, of, oq, os, ob, ld_o, batch, heads, L, scale, stream);
   constexpr int LP = 16 * NT, NW = 8;
   const size_t lds = (size_t)2 * LP * ROW_B + (size_t)LP * 4 + (size_t)NW * 16 * (HD + 4) * 4;
   static bool done = false;
-  if (allow_lds_once(self_attn_bf16_mx_kernel<NT, NW>, lds, done, "self_attn_fwd_bf16")) return LR2_ERR_LAUNCH;
-  LR2_LAUNCH((self_attn_bf16_mx_kernel<NT, NW>), dim3(1, heads, batch), dim3(64 * NW), lds, stream, q, k, v, ld, seg, of, oq, os, ob,
+  if (allow_lds_once(self_attn_plane_kernel<F16, NT, NW>, lds, done, F16 ? "self_attn_fwd_f16" : "self_attn_fwd_bf16")) return LR2_ERR_LAUNCH;
+  LR2_LAUNCH((self_attn_plane_kernel<F16, NT, NW>), dim3(1, heads, batch), dim3(64 * NW), lds, stream, q, k, v, ld, seg, of, oq, os, ob,
              ld_o, heads, L, scale);
-  return lr2_launch_status("lr2_self_attn_fwd_bf16");
+  return lr2_launch_status(F16 ? "lr2_self_attn_fwd_f16" : "lr2_self_attn_fwd_bf16");
 }
+
+uint64_t g_launches_f16 = 0;     // accepted calls of lr2_self_attn_fwd_f16 (host-side counter)
 
 }  // namespace
 
@@ -447,7 +442,29 @@ extern "C" int lr2_self_attn_fwd_bf16(const void* q, const void* k, const void* 
   if (head_dim != HD || L > 288 || (ld % 8) || ld_o < heads * HD || (ld_o % 32)) return LR2_ERR_SHAPE;
   const bf16_t *qq = (const bf16_t*)q, *kk = (const bf16_t*)k, *vv = (const bf16_t*)v;
   hipStream_t s = (hipStream_t)stream;
-#define GO(NT) return launch<NT>(qq, kk, vv, ld, seg, (float*)o_f32, (uint8_t*)o_q, (uint8_t*)o_scales, (bf16_t*)o_bf16, ld_o, batch, heads, L, scale, s)
+#define GO(NT) return launch<false, NT>(qq, kk, vv, ld, seg, (float*)o_f32, (uint8_t*)o_q, (uint8_t*)o_scales, (bf16_t*)o_bf16, ld_o, batch, heads, L, scale, s)
+  if (L <= 64) GO(4);
+  if (L <= 128) GO(8);
+  if (L <= 224) GO(14);
+  GO(18);
+#undef GO
+}
+
+// the same kernels on f16 planes (the "f16" inference mode): no MX-FP8 outputs, its own argument checks
+extern "C" int lr2_self_attn_fwd_f16_launch_count(uint64_t* count) {
+  if (!count) return LR2_ERR_ARG;
+  *count = g_launches_f16;
+  return 0;
+}
+
+extern "C" int lr2_self_attn_fwd_f16(const void* q, const void* k, const void* v, int ld, const int64_t* seg, void* o_f32, void* o_f16,
+                                     int ld_o, int batch, int heads, int L, int head_dim, float scale, void* stream) {
+  if (!q || !k || !v || !seg || (!o_f32 && !o_f16) || batch <= 0 || heads <= 0 || L <= 0) return LR2_ERR_ARG;
+  if (head_dim != HD || L > 288 || ld < heads * HD || (ld % 8) || ld_o < heads * HD || (ld_o % 4)) return LR2_ERR_SHAPE;
+  const f16_t *qq = (const f16_t*)q, *kk = (const f16_t*)k, *vv = (const f16_t*)v;
+  hipStream_t s = (hipStream_t)stream;
+  ++g_launches_f16;
+#define GO(NT) return launch<true, NT>(qq, kk, vv, ld, seg, (float*)o_f32, nullptr, nullptr, (f16_t*)o_f16, ld_o, batch, heads, L, scale, s)
   if (L <= 64) GO(4);
   if (L <= 128) GO(8);
   if (L <= 224) GO(14);

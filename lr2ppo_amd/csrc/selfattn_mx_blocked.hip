@@ -16,6 +16,10 @@
 // block and meets every barrier, only its stores are skipped.
 // The epilogue is the store half of selfattn_mx.hip's mx_phase_b: accumulator / l through the wave's private [16][HD + 4] fp32 slab, rows
 // out as float4, through store_bf16x4 (round to nearest even), and as MX-FP8 by lr2_quant_mxfp8's rule per 32-column block.
+//
+// The same kernel serves the f16 inference mode above 288 tokens (FeatureExtractor(precision="f16", f16_attention_long=True);
+// lr2_self_attn_fwd_f16_blocked below) through its compile-time parameter F16, as selfattn_mx.hip's kernels do: f16 planes in, fp32
+// and / or ONE f16 plane out, no MX-FP8; one parameter list for both formats, null Oq / Os in f16.
 
 #include "selfattn_b1.h"
 
@@ -23,13 +27,13 @@ namespace {
 
 constexpr int MXL_SLOTS = 4;       // query sub-tiles a wave carries across the key blocks
 
-template <int NT, int NW, int SLOTS>
-__global__ __launch_bounds__(64 * NW) void self_attn_bf16_mx_blocked_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
-                                                                            const bf16_t* __restrict__ V, int ld,
-                                                                            const int64_t* __restrict__ seg, float* __restrict__ Of,
-                                                                            uint8_t* __restrict__ Oq, uint8_t* __restrict__ Os,
-                                                                            bf16_t* __restrict__ Ob, int ld_o, int heads, int L,
-                                                                            float scale, int n_blocks) {
+template <bool F16, int NT, int NW, int SLOTS>
+__global__ __launch_bounds__(64 * NW) void self_attn_plane_blocked_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
+                                                                          const bf16_t* __restrict__ V, int ld,
+                                                                          const int64_t* __restrict__ seg, float* __restrict__ Of,
+                                                                          uint8_t* __restrict__ Oq, uint8_t* __restrict__ Os,
+                                                                          bf16_t* __restrict__ Ob, int ld_o, int heads, int L,
+                                                                          float scale, int n_blocks) {
   constexpr int LP = 16 * NT;
   constexpr int PLANE = LP * ROW_B;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -104,7 +108,7 @@ __global__ __launch_bounds__(64 * NW) void self_attn_bf16_mx_blocked_kernel(cons
 #pragma unroll
           for (int ks = 0; ks < 2; ++ks) {
             const bf16x8_t kf = *reinterpret_cast<const bf16x8_t*>(sK + k_off(16 * t + qn, g + 4 * ks));
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, q[j][ks], acc, 0, 0, 0);
+            acc = mfma_plane<F16>(kf, q[j][ks], acc);
           }
           s[t] = acc;
         }
@@ -143,14 +147,14 @@ __global__ __launch_bounds__(64 * NW) void self_attn_bf16_mx_blocked_kernel(cons
         const int i16 = lane & 15, tq = i16 >> 2, tp = i16 & 3;
 #pragma unroll
         for (int u = 0; u < NT / 2; ++u) {
-          const u32x4_t pw = {cvt_pk_bf16(s[2 * u][0], s[2 * u][1]), cvt_pk_bf16(s[2 * u][2], s[2 * u][3]),
-                              cvt_pk_bf16(s[2 * u + 1][0], s[2 * u + 1][1]), cvt_pk_bf16(s[2 * u + 1][2], s[2 * u + 1][3])};
+          const u32x4_t pw = {prob_pk<F16>(s[2 * u][0], s[2 * u][1]), prob_pk<F16>(s[2 * u][2], s[2 * u][3]),
+                              prob_pk<F16>(s[2 * u + 1][0], s[2 * u + 1][1]), prob_pk<F16>(s[2 * u + 1][2], s[2 * u + 1][3])};
           const bf16x8_t pf = __builtin_bit_cast(bf16x8_t, pw);
           const int ra = 32 * u + 4 * g + tq, rb = ra + 16;
 #pragma unroll
           for (int n = 0; n < 4; ++n) {
             const bf16x8_t vf = tr_pair(sV, ra, rb, 2 * n + (tp >> 1), 8 * (tp & 1));
-            o[j][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf, vf, o[j][n], 0, 0, 0);
+            o[j][n] = mfma_plane<F16>(pf, vf, o[j][n]);
           }
         }
       }
@@ -183,20 +187,11 @@ __global__ __launch_bounds__(64 * NW) void self_attn_bf16_mx_blocked_kernel(cons
         const float4 v = *reinterpret_cast<const float4*>(slab + r * (HD + 4) + c);
         const size_t lrow = (size_t)(ok ? qr : 0);
         if (Of && ok) *reinterpret_cast<float4*>(Of + ubase + (lrow * (size_t)ld_o + (size_t)c)) = v;
-        if (Ob && ok) store_bf16x4(Ob + ubase + (lrow * (size_t)ld_o + (size_t)c), v);       // ONE bf16 plane: RNE of the fp32 context
-        if (Oq) {
+        if (Ob && ok) store_plane4<F16>(Ob + ubase + (lrow * (size_t)ld_o + (size_t)c), v);  // ONE bf16 / f16 plane: RNE of the fp32 context
+        if (!F16 && Oq) {
           // the row's 32-column MX block = 8 consecutive lanes x 4 columns (the head's 64 columns are two blocks): as lr2_quant_mxfp8
-          float amax = fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
-          amax = group8_max(amax);
-          int e = (int)((__float_as_uint(amax) >> 23) & 0xFF) - 127 - 8;
-          if (amax < 1.17549435e-38f) e = -127;
-          if (e < -127) e = -127;
-          if (e > 127) e = 127;
-          const uint32_t ef = (uint32_t)(127 - e);
-          const float sc = __uint_as_float(ef ? ef << 23 : 0x00400000u);
-          int w = 0;
-          w = __builtin_amdgcn_cvt_pk_fp8_f32(__builtin_amdgcn_fmed3f(v.x * sc, -448.f, 448.f), __builtin_amdgcn_fmed3f(v.y * sc, -448.f, 448.f), w, false);
-          w = __builtin_amdgcn_cvt_pk_fp8_f32(__builtin_amdgcn_fmed3f(v.z * sc, -448.f, 448.f), __builtin_amdgcn_fmed3f(v.w * sc, -448.f, 448.f), w, true);
+          int e;
+          const int w = mx_quant4_group8(v, e);
           if (ok) {
             *reinterpret_cast<int*>(Oq + ubase + (lrow * (size_t)ld_o + (size_t)c)) = w;
             if ((ln & 7) == 0) Os[sbase + (lrow * (size_t)(ld_o / 32) + (size_t)(c >> 5))] = (uint8_t)(e + 127);
@@ -209,20 +204,22 @@ __global__ __launch_bounds__(64 * NW) void self_attn_bf16_mx_blocked_kernel(cons
 }
 
 // ---- launcher ----
-uint64_t g_mxl_launches = 0;     // accepted calls since load (lr2_self_attn_fwd_bf16_blocked_launch_count)
+uint64_t g_mxl_launches = 0;      // accepted calls since load (lr2_self_attn_fwd_bf16_blocked_launch_count)
+uint64_t g_f16l_launches = 0;     // ... of the f16 entry point (lr2_self_attn_fwd_f16_blocked_launch_count)
 
-template <int NT>
+template <bool F16, int NT>
 int mxl_launch(const bf16_t* q, const bf16_t* k, const bf16_t* v, int ld, const int64_t* seg, float* of, uint8_t* oq, uint8_t* os,
                bf16_t* ob, int ld_o, int batch, int heads, int L, float scale, hipStream_t stream) {
   constexpr int LP = 16 * NT, NW = B1_NW, SLOTS = MXL_SLOTS;
   const size_t lds = (size_t)2 * LP * ROW_B + (size_t)LP * 4 + (size_t)NW * 16 * (HD + 4) * 4;
   static bool done = false;
-  if (allow_lds_once(self_attn_bf16_mx_blocked_kernel<NT, NW, SLOTS>, lds, done, "self_attn_fwd_bf16_blocked")) return LR2_ERR_LAUNCH;
+  if (allow_lds_once(self_attn_plane_blocked_kernel<F16, NT, NW, SLOTS>, lds, done, F16 ? "self_attn_fwd_f16_blocked" : "self_attn_fwd_bf16_blocked"))
+    return LR2_ERR_LAUNCH;
   const int n_sub = (L + 15) / 16;
   const int chunks = (n_sub + NW * SLOTS - 1) / (NW * SLOTS);
-  LR2_LAUNCH((self_attn_bf16_mx_blocked_kernel<NT, NW, SLOTS>), dim3(chunks, heads, batch), dim3(64 * NW), lds, stream, q, k, v, ld, seg, of,
+  LR2_LAUNCH((self_attn_plane_blocked_kernel<F16, NT, NW, SLOTS>), dim3(chunks, heads, batch), dim3(64 * NW), lds, stream, q, k, v, ld, seg, of,
              oq, os, ob, ld_o, heads, L, scale, (L + LP - 1) / LP);
-  return lr2_launch_status("lr2_self_attn_fwd_bf16_blocked");
+  return lr2_launch_status(F16 ? "lr2_self_attn_fwd_f16_blocked" : "lr2_self_attn_fwd_bf16_blocked");
 }
 
 }  // namespace
@@ -241,7 +238,7 @@ extern "C" int lr2_self_attn_fwd_bf16_blocked(const void* q, const void* k, cons
   const bf16_t *qq = (const bf16_t*)q, *kk = (const bf16_t*)k, *vv = (const bf16_t*)v;
   hipStream_t s = (hipStream_t)stream;
   int rc = LR2_ERR_LAUNCH;      // a plan this dispatch does not know is an error, not another block
-#define GO(NT) rc = mxl_launch<NT>(qq, kk, vv, ld, seg, (float*)o_f32, (uint8_t*)o_q, (uint8_t*)o_scales, (bf16_t*)o_bf16, ld_o, batch, heads, L, scale, s)
+#define GO(NT) rc = mxl_launch<false, NT>(qq, kk, vv, ld, seg, (float*)o_f32, (uint8_t*)o_q, (uint8_t*)o_scales, (bf16_t*)o_bf16, ld_o, batch, heads, L, scale, s)
   if (block == 160) GO(10);
   else if (block == 192) GO(12);
   else if (block == 224) GO(14);
@@ -253,5 +250,33 @@ extern "C" int lr2_self_attn_fwd_bf16_blocked(const void* q, const void* k, cons
 extern "C" int lr2_self_attn_fwd_bf16_blocked_launch_count(uint64_t* count) {
   if (!count) return LR2_ERR_ARG;
   *count = g_mxl_launches;
+  return 0;
+}
+
+// the same kernel on f16 planes (the "f16" inference mode with f16_attention_long): no MX-FP8 outputs, its own argument checks
+extern "C" int lr2_self_attn_fwd_f16_blocked(const void* q, const void* k, const void* v, int ld, const int64_t* seg, void* o_f32,
+                                             void* o_f16, int ld_o, int batch, int heads, int L, int head_dim, float scale,
+                                             void* stream) {
+  if (!q || !k || !v || !seg || (!o_f32 && !o_f16) || batch <= 0 || heads <= 0) return LR2_ERR_ARG;
+  if (!b1_aligned16(q) || !b1_aligned16(k) || !b1_aligned16(v) || !b1_aligned16(o_f32) || ((uintptr_t)o_f16 & 7)) return LR2_ERR_ARG;
+  if (head_dim != HD || L < 1 || ld < heads * HD || ld_o < heads * HD || (ld % 8) || (ld_o % 4)) return LR2_ERR_SHAPE;
+  // the block length is the bf16 kernels': one rule in one place
+  int block = 0;
+  if (lr2_self_attn_bf16_blocked_plan(L, &block, nullptr, nullptr)) return LR2_ERR_LAUNCH;
+  const f16_t *qq = (const f16_t*)q, *kk = (const f16_t*)k, *vv = (const f16_t*)v;
+  hipStream_t s = (hipStream_t)stream;
+  int rc = LR2_ERR_LAUNCH;      // a plan this dispatch does not know is an error, not another block
+#define GO(NT) rc = mxl_launch<true, NT>(qq, kk, vv, ld, seg, (float*)o_f32, nullptr, nullptr, (f16_t*)o_f16, ld_o, batch, heads, L, scale, s)
+  if (block == 160) GO(10);
+  else if (block == 192) GO(12);
+  else if (block == 224) GO(14);
+#undef GO
+  if (rc == 0) ++g_f16l_launches;
+  return rc;
+}
+
+extern "C" int lr2_self_attn_fwd_f16_blocked_launch_count(uint64_t* count) {
+  if (!count) return LR2_ERR_ARG;
+  *count = g_f16l_launches;
   return 0;
 }

@@ -171,7 +171,7 @@ class FeatureExtractor(nn.Module):
     operand too, on the key-blocked kernel of csrc/selfattn_mx_blocked.hip instead of the 3-pass attention
     (TransformerEncoder.infer_attention_long); sequences up to 288 are unaffected.
     f16_attention_long ("f16" only): that mode runs sequences longer than 288 (head_dim 64) on ONE f16 plane per operand too, on the
-    key-blocked kernel of csrc/selfattn_f16_blocked.hip instead of the 3-pass attention (TransformerEncoder.f16_attention_long,
+    key-blocked kernel of csrc/selfattn_mx_blocked.hip instead of the 3-pass attention (TransformerEncoder.f16_attention_long,
     DESIGN 4.5); sequences up to 288 are unaffected.
     recompute: the training forwards of both towers keep each layer's input only and the backward re-runs a layer's forward right
     before that layer's backward (TransformerEncoder.recompute): the same bits, ~1/12 of the activation memory, one more

@@ -700,7 +700,7 @@ def self_attn_fwd_f16_launch_count() -> int:
 
 def self_attn_fwd_f16_blocked(qkv: torch.Tensor, seg, *, batch, heads, L, head_dim, scale, out: Optional[torch.Tensor] = None,
                               out_plane: Optional[torch.Tensor] = None):
-    """self_attn_fwd_f16 with the keys walked in blocks through LDS (lr2_self_attn_fwd_f16_blocked, csrc/selfattn_f16_blocked.hip): the
+    """self_attn_fwd_f16 with the keys walked in blocks through LDS (lr2_self_attn_fwd_f16_blocked, csrc/selfattn_mx_blocked.hip): the
     same arguments, checks and outputs at any L >= 1 -- what the f16 inference schedule runs above 288 tokens with
     TransformerEncoder.f16_attention_long."""
     E = heads * head_dim

@@ -182,7 +182,7 @@ class TransformerEncoder(nn.Module):
     # FeatureExtractor(precision="bf16" | "mxfp8", attention_long=True)); off: the 3-pass attention kernels above 288
     infer_attention_long = False
     # True: the f16 inference schedule (forward_f16) runs a layer with head_dim 64 and L > 288 on ONE f16 plane per operand too, on the
-    # key-blocked kernel of csrc/selfattn_f16_blocked.hip (ops.self_attn_fwd_f16_blocked; FeatureExtractor(precision="f16",
+    # key-blocked kernel of csrc/selfattn_mx_blocked.hip (ops.self_attn_fwd_f16_blocked; FeatureExtractor(precision="f16",
     # f16_attention_long=True)); off: the 3-pass attention kernels above 288
     f16_attention_long = False
 

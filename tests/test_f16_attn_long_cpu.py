@@ -1,5 +1,5 @@
 """Key-blocked f16 attention above 288 tokens for the f16 inference mode (FeatureExtractor(precision="f16", f16_attention_long=True);
-csrc/selfattn_f16_blocked.hip), the parts that need no GPU: lr2_self_attn_fwd_f16_blocked rejects bad arguments with the code its header
+csrc/selfattn_mx_blocked.hip), the parts that need no GPU: lr2_self_attn_fwd_f16_blocked rejects bad arguments with the code its header
 names before launching anything, the switch's combinations at the constructor, the launchers' flag and tools/encoder_bench.py's command
 line, and the ABI number, which the two additive entry points leave at 27."""
 import argparse
@@ -179,4 +179,6 @@ def test_abi_number_stays_27_and_the_names_are_bound():
         assert name in native.SIGNATURES and re.search(r"\bint %s\(" % name, hdr), name
         assert getattr(native.lib(), name) is not None
     assert native.SIGNATURES["lr2_self_attn_fwd_f16_blocked"] == native.SIGNATURES["lr2_self_attn_fwd_f16"]
-    assert "selfattn_f16_blocked.hip" in native.SOURCES
+    defining = [s for s in os.listdir(native.CSRC) if s.endswith(".hip")
+                and 'extern "C" int lr2_self_attn_fwd_f16_blocked(' in open(os.path.join(native.CSRC, s)).read()]
+    assert len(defining) == 1 and defining[0] in native.SOURCES, defining

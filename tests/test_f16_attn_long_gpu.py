@@ -1,5 +1,5 @@
 """Key-blocked f16 attention above 288 tokens for the f16 inference mode: lr2_self_attn_fwd_f16_blocked
-(csrc/selfattn_f16_blocked.hip) at the kernel level through ops.self_attn_fwd_f16_blocked, TransformerEncoder.f16_attention_long in
+(csrc/selfattn_mx_blocked.hip) at the kernel level through ops.self_attn_fwd_f16_blocked, TransformerEncoder.f16_attention_long in
 forward_f16 above it, and FeatureExtractor(precision="f16", f16_attention_long=True) at the top.
 
 Structure, inputs and helpers are test_bf16_attn_infer_long_gpu.py's: attn_cases.exact_qkv at scale 1/8 -- small integers times a power

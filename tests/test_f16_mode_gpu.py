@@ -1,7 +1,7 @@
 """The single-pass f16 inference mode on a real MI355X: the 256 x 256 f16 product (csrc/gemm256_f16.hip) against exact and fp64
 references -- integers, 11-bit operands a bf16 instruction or plane would round, the fp32 accumulation bound --, the f16 plane writer
 of the product / LayerNorm / lr2_round_f16 / attention byte for byte against round-to-nearest-even of the fp32 results (subnormal range
-and saturation included), the attention (csrc/selfattn_f16.hip) against fp64 and against the bf16 kernel's distance from it,
+and saturation included), the attention (csrc/selfattn_mx.hip) against fp64 and against the bf16 kernel's distance from it,
 TransformerEncoder.forward_f16 against an fp64 emulation that rounds to f16 where the schedule writes a plane, and
 FeatureExtractor(precision="f16") against the split-bf16 path AND the bf16 mode of the same weights: at most a quarter of the bf16
 mode's distance (three more significand bits: 8 x expected).
