@@ -119,15 +119,24 @@ int lr2_gemm_launch_counts(uint64_t counts[3]);
  * CUs idle that a round of 192-row tiles fills.  Pure host arithmetic (no device call); tests assert which form a shape reaches. */
 int lr2_gemm256_tile_rows(int M, int N, int* rows);
 
-/* Row gather: dst[b, j, :] = src[b, index[b, j], :]  (rows of row_elems fp32; strides in elements).
+/* Row gather: dst[b, j, :] = src[b, clamp(index[b, j]), :]  (rows of row_elems fp32; strides in elements; index NULL: index[b, j] = j).
+ * An index outside [0, t_in) is CLAMPED into it (below 0 -> row 0, t_in and above -> row t_in - 1): never an out-of-bounds read, and
+ * with index NULL and t_in = 1 every output row is the one source row.  lr2_gather_rows_bwd applies the same clamp, so the pair is
+ * adjoint for every index tensor.
+ * LR2_ERR_ARG: a NULL src / dst, B / t_in / t_out <= 0, row_elems == 0.  LR2_ERR_SHAPE: row_elems or a stride % 4, src or dst not
+ * 16-byte aligned (float4 accesses).
  * replaces: text_emb[batch_index, index] / img_emb[batch_index, index] (finetune/ppo.py:268-271,321-324). */
 int lr2_gather_rows(const void* src, const int64_t* index, void* dst, int B, int t_in, int t_out, uint64_t row_elems,
                     uint64_t src_bstride, uint64_t src_tstride, void* stream);
-/* Scatter-add of row gradients: dsrc[b, index[b,j], :] += ddst[b, j, :]  (dsrc must be zero-initialised). */
+/* Gradient of lr2_gather_rows with tight strides: dsrc[b, t, :] = sum over the j with clamp(index[b, j]) == t of ddst[b, j, :], in j
+ * order.  EVERY row of dsrc [B, t_in, row_elems] is overwritten (a row that no j selects becomes zeros): no zero-initialisation,
+ * no accumulation into dsrc.  The clamp is lr2_gather_rows'.  Refusals as in lr2_gather_rows (ddst and dsrc 16-byte aligned). */
 int lr2_gather_rows_bwd(const void* ddst, const int64_t* index, void* dsrc, int B, int t_in, int t_out,
                         uint64_t row_elems, void* stream);
 /* Strided row copy: dst[(r / group)*dst_gstride + (r % group)*D + dst_off + c] = src[r*D + c].
  * dst_planes=1: dst is a bf16 planes tensor (same element offsets, lo plane dst_lo_off elements later).
+ * LR2_ERR_ARG: NULL src / dst, rows / D / group <= 0.  LR2_ERR_SHAPE: D, dst_gstride or dst_off % 4; src not 16-byte aligned; dst not
+ * 16-byte aligned (fp32) or not 8-byte aligned / dst_lo_off % 4 (planes).
  * replaces: torch.cat([x, img_feature], dim=1) (finetune/ppo.py:224). */
 int lr2_copy_rows(const void* src, void* dst, int dst_planes, uint64_t dst_lo_off, int rows, int D, int group,
                   uint64_t dst_gstride, uint64_t dst_off, void* stream);
@@ -194,11 +203,14 @@ int lr2_colsum(const void* x, int is_planes, uint64_t lo_off, int rows, int cols
 /* XiT multi-head attention core, per (sequence b, head h): S = Q K^T (no pre-scale), P = softmax(S) * post_scale,
  * O = P V.  Q/O: [batch*Lq, heads*hd]; K/V: [batch*Lk, heads*hd].  Lq<=256, Lk<=16, hd<=96, hd%4==0.
  * o_planes=1: O is written as bf16 planes (hi at O, lo o_lo_off elements later) for the projection GEMM.
+ * LR2_ERR_SHAPE: Lq outside [1, 256], Lk outside [1, 16], head_dim outside [4, 96] or % 4; Q not 16-byte aligned; O not 16-byte
+ * aligned (fp32) or not 8-byte aligned / o_lo_off % 4 (planes).
  * replaces: finetune/xit.py:133-146 (einsum, softmax, "/ scaling", einsum). */
 int lr2_xattn_fwd(const void* Q, const void* K, const void* V, void* O, int o_planes, uint64_t o_lo_off, int batch,
                   int heads, int Lq, int Lk, int head_dim, float post_scale, void* stream);
 /* Backward of lr2_xattn_fwd: recomputes P; writes dQ [batch*Lq, E], dK, dV [batch*Lk, E] (fp32, or bf16 planes when
- * planes=1: lo planes q_lo_off / kv_lo_off elements after the hi planes). */
+ * planes=1: lo planes q_lo_off / kv_lo_off elements after the hi planes).  Shape rules of the forward; Q and dO 16-byte aligned;
+ * dQ / dK / dV 16-byte aligned (fp32) or 8-byte aligned with q_lo_off % 4 == 0 and kv_lo_off % 4 == 0 (planes), else LR2_ERR_SHAPE. */
 int lr2_xattn_bwd(const void* Q, const void* K, const void* V, const void* dO, void* dQ, void* dK, void* dV,
                   int planes, uint64_t q_lo_off, uint64_t kv_lo_off, int batch, int heads, int Lq, int Lk, int head_dim,
                   float post_scale, void* stream);
@@ -338,7 +350,9 @@ int lr2_step_scalars_store(void* dst_dev, uint64_t seed, const float* lrs_host, 
 
 /* Tokens -> embeddings: out[r,:] = word[src[r]] + pos[r % L] + seg_table[seg[r]].  Ids outside [0, vocab) / [0, n_seg) never
  * index memory: the row is taken from index 0 and *err_flag (device int, may be NULL) gets bit 0 (token) / bit 1 (segment)
- * OR-ed in, for the host to raise the IndexError nn.Embedding would.
+ * OR-ed in, for the host to raise the IndexError nn.Embedding would.  The sum is (word + pos) + seg in fp32.
+ * LR2_ERR_ARG: a NULL pointer (err_flag excepted), rows / L / D / vocab / n_seg <= 0.  LR2_ERR_SHAPE: D % 4; word, pos, seg_table or
+ * out not 16-byte aligned (float4 accesses).
  * replaces: tencentpretrain/embeddings/{word,pos,seg}_embedding.py forward sums (embedding.py:19-30). */
 int lr2_text_embed(const int64_t* src, const int64_t* seg, const void* word, const void* pos, const void* seg_table,
                    void* out, int rows, int L, int D, int64_t vocab, int n_seg, int* err_flag, void* stream);
@@ -348,7 +362,10 @@ int lr2_text_embed(const int64_t* src, const int64_t* seg, const void* word, con
  * summed in original row order inside pieces of LR2_TEXT_EMBED_BWD_WORD_SEG sorted positions, the pieces of a long run (the padding
  * id) in piece order through `word_partials` (fp32 scratch, 2 * ceil(rows / LR2_TEXT_EMBED_BWD_WORD_SEG) * D floats) -- a fixed
  * order, and no single workgroup walks a long run alone.  dseg[s, :] = sum of dx rows with segment s via `seg_partials` (fp32
- * scratch, ceil(rows / LR2_TEXT_EMBED_BWD_ROWS_PER_BLOCK) * n_seg * D floats).  No atomics.
+ * scratch, ceil(rows / LR2_TEXT_EMBED_BWD_ROWS_PER_BLOCK) * n_seg * D floats).  No atomics.  Rows whose token id is outside [0, vocab)
+ * or whose segment id is outside [0, n_seg) are dropped from the respective sum.
+ * LR2_ERR_ARG: a NULL pointer, rows / D / vocab <= 0.  LR2_ERR_SHAPE: D % 4, n_seg outside [1, 4]; dx, dword or word_partials not
+ * 16-byte aligned (float4 accesses).
  * replaces: autograd of nn.Embedding in tencentpretrain/embeddings/{word,seg}_embedding.py. */
 #define LR2_TEXT_EMBED_BWD_ROWS_PER_BLOCK 64
 #define LR2_TEXT_EMBED_BWD_WORD_SEG 256
@@ -361,12 +378,16 @@ int lr2_text_embed_bwd(const void* dx, const int64_t* sorted_ids, const int64_t*
 int lr2_dropout_apply(const void* src, void* dst, uint64_t n, float drop_p, uint64_t drop_seed, uint32_t drop_site,
                       void* stream);
 /* Image -> patch rows: out[(b*P + p), c*ps*ps + i*ps + j] = img[b, c, py*ps+i, px*ps+j].
+ * LR2_ERR_ARG: NULL img / out, B / C / H / W / ps <= 0.  LR2_ERR_SHAPE: H or W % ps.
  * replaces: the unfold implied by nn.Conv2d(k=s=patch) in tencentpretrain/embeddings/patch_embedding.py:18,27. */
 int lr2_patchify(const void* img, void* out, int B, int C, int H, int W, int ps, void* stream);
 /* Image -> patch rows as bf16 hi/lo planes (the A operand of the patch-projection GEMM); element layout of lr2_patchify with row
  * stride ld >= C*ps*ps (columns past C*ps*ps are written as zeros: ViT-L/14's 588 -> 640 so the GEMM sees whole K tiles); ps even.
  * img: fp32 [B,C,H,W] (is_u8 = 0) or uint8 frames [B,C,H,W] (is_u8 = 1); with is_u8 and mean3/std3 (HOST float[3]) given, pixels
  * are normalised on the fly: (x / 255 - mean[c]) / std[c].
+ * LR2_ERR_ARG: NULL img / out_hi, B / C / H / W / ps <= 0.  LR2_ERR_SHAPE: H or W % ps, C > 3, ps odd, ld < C*ps*ps, ld % 4, lo_off
+ * odd; out_hi not 8-byte aligned when ps % 4 == 0 and lo_off % 4 == 0 (4 x bf16 stores per plane), not 4-byte aligned otherwise
+ * (2 x bf16 stores); img not 16-byte aligned when ps == 16, ld == C*ps*ps and lo_off % 4 == 0 (the strip kernel's 16-byte loads).
  * replaces: ZeroOneNormalize + transforms.Normalize (tencentpretrain/utils/dataloader.py:559-561) + the unfold implied by
  * nn.Conv2d(k=s=patch) (embeddings/patch_embedding.py:18,27). */
 int lr2_patchify_planes(const void* img, int is_u8, void* out_hi, uint64_t lo_off, int ld, int B, int C, int H, int W, int ps,
@@ -379,6 +400,7 @@ int lr2_patchify_planes(const void* img, int is_u8, void* out_hi, uint64_t lo_of
 int lr2_ndcg(const void* scores, const int64_t* gold, const int64_t* offsets, const void* disc, const int64_t* ks, int n_k,
              void* out, int n_items, void* stream);
 /* ViT embedding assembly: out[b,0,:] = cls + pos[0]; out[b,1+p,:] = patch_proj[b*P+p,:] + pos[1+p].
+ * LR2_ERR_ARG: a NULL pointer, B / P / D <= 0.  LR2_ERR_SHAPE: D % 4; patch_proj, cls, pos or out not 16-byte aligned (float4).
  * replaces: patch_embedding.py:28-29 (cls concat) + pos_embedding.py:30-35 + embedding.py:27-30. */
 int lr2_vit_assemble(const void* patch_proj, const void* cls, const void* pos, void* out, int B, int P, int D,
                      void* stream);

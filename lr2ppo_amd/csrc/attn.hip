@@ -211,7 +211,9 @@ __global__ __launch_bounds__(256) void xattn_bwd_kernel(const float* __restrict_
 extern "C" int lr2_xattn_fwd(const void* Q, const void* K, const void* V, void* O, int o_planes, uint64_t o_lo_off, int batch,
                              int heads, int Lq, int Lk, int head_dim, float post_scale, void* stream) {
   if (!Q || !K || !V || !O || batch <= 0 || heads <= 0) return LR2_ERR_ARG;
-  if (Lq < 1 || Lq > 256 || Lk < 1 || Lk > MAX_LK || head_dim > MAX_HD || head_dim % 4 != 0) return LR2_ERR_SHAPE;
+  if (Lq < 1 || Lq > 256 || Lk < 1 || Lk > MAX_LK || head_dim < 4 || head_dim > MAX_HD || head_dim % 4 != 0) return LR2_ERR_SHAPE;
+  if (misaligned(Q, 16)) return LR2_ERR_SHAPE;                                  // float4 loads (K, V: element loads into LDS)
+  if (o_planes ? (misaligned(O, 8) || o_lo_off % 4) : misaligned(O, 16)) return LR2_ERR_SHAPE;   // 4 x bf16 per plane / float4
   LR2_LAUNCH(xattn_fwd_kernel, dim3(batch * heads), dim3(256), 0, (hipStream_t)stream, (const float*)Q,
                      (const float*)K, (const float*)V, (float*)O, o_planes, (size_t)o_lo_off, heads, Lq, Lk, head_dim, post_scale);
   return lr2_launch_status(__func__);
@@ -221,7 +223,11 @@ extern "C" int lr2_xattn_bwd(const void* Q, const void* K, const void* V, const 
                              int planes, uint64_t q_lo_off, uint64_t kv_lo_off, int batch, int heads, int Lq, int Lk,
                              int head_dim, float post_scale, void* stream) {
   if (!Q || !K || !V || !dO || !dQ || !dK || !dV || batch <= 0 || heads <= 0) return LR2_ERR_ARG;
-  if (Lq < 1 || Lq > 256 || Lk < 1 || Lk > MAX_LK || head_dim > MAX_HD || head_dim % 4 != 0) return LR2_ERR_SHAPE;
+  if (Lq < 1 || Lq > 256 || Lk < 1 || Lk > MAX_LK || head_dim < 4 || head_dim > MAX_HD || head_dim % 4 != 0) return LR2_ERR_SHAPE;
+  if (misaligned(Q, 16) || misaligned(dO, 16)) return LR2_ERR_SHAPE;            // float4 loads (K, V: element loads into LDS)
+  if (planes ? (misaligned(dQ, 8) || misaligned(dK, 8) || misaligned(dV, 8) || q_lo_off % 4 || kv_lo_off % 4)
+             : (misaligned(dQ, 16) || misaligned(dK, 16) || misaligned(dV, 16)))
+    return LR2_ERR_SHAPE;                                                       // 4 x bf16 per plane / float4 stores
   const size_t lds = sizeof(float) * ((size_t)2 * MAX_LK * MAX_HD + 2 * 256 * MAX_LK + 2 * 2 * MAX_LK * (MAX_HD + 1));
   static bool attr_set = false;
   if (!attr_set) {

@@ -291,6 +291,9 @@ static inline int lr2_launch_status(const char* what) {
   fprintf(stderr, "lr2ppo_hip: %s: %s\n", what, hipGetErrorString(e));
   return -3;
 }
+// a pointer that a kernel's vector access (float4 / uint4: 16 bytes, 4 x bf16: 8 bytes, 2 x bf16: 4 bytes) cannot take:
+// LR2_ERR_SHAPE, never a launch
+static inline bool misaligned(const void* p, uintptr_t bytes) { return ((uintptr_t)p % bytes) != 0; }
 // Raise a kernel's dynamic-LDS limit.  hipFuncGetAttributes first: it forces the lazily loaded code object in,
 // without which hipFuncSetAttribute can fail when this is the first kernel the process touches.
 template <typename K>

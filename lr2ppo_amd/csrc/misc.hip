@@ -21,7 +21,7 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restric
   for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (uint64_t)gridDim.x * 256) d[i] = s[i];
 }
 
-// dsrc[b, t, :] = sum over j with index[b, j] == t of ddst[b, j, :]   (deterministic, no atomics)
+// dsrc[b, t, :] = sum over j with clamp(index[b, j]) == t of ddst[b, j, :]   (deterministic, no atomics; every row is written)
 __global__ __launch_bounds__(256) void gather_rows_bwd_kernel(const float* __restrict__ ddst, const int64_t* __restrict__ index,
                                                               float* __restrict__ dsrc, int t_in, int t_out,
                                                               uint64_t row_elems) {
@@ -32,7 +32,9 @@ __global__ __launch_bounds__(256) void gather_rows_bwd_kernel(const float* __res
   for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (uint64_t)gridDim.x * 256) {
     float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int j = 0; j < t_out; ++j) {
-      const int64_t st = index ? index[(size_t)b * t_out + j] : j;
+      int64_t st = index ? index[(size_t)b * t_out + j] : j;
+      if (st < 0) st = 0;                       // the forward's clamp: the pair stays adjoint for every index
+      if (st >= t_in) st = t_in - 1;
       if (st == t) {
         const float4 v = reinterpret_cast<const float4*>(ddst + ((size_t)b * t_out + j) * row_elems)[i];
         a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
@@ -836,8 +838,6 @@ inline int grid_for(size_t work_items, int cap = 4096) {
   return (int)b;
 }
 #define CHECK_LAUNCH() return lr2_launch_status(__func__)
-// a pointer that a kernel's vector access (float4: 16 bytes, 4 x bf16: 8 bytes) cannot take: LR2_ERR_SHAPE, never a launch
-inline bool misaligned(const void* p, uintptr_t bytes) { return ((uintptr_t)p % bytes) != 0; }
 
 }  // namespace
 
@@ -858,8 +858,9 @@ extern "C" int lr2_device_info(char* name, int len) {
 
 extern "C" int lr2_gather_rows(const void* src, const int64_t* index, void* dst, int B, int t_in, int t_out,
                                uint64_t row_elems, uint64_t src_bstride, uint64_t src_tstride, void* stream) {
-  if (!src || !dst || B <= 0 || t_in <= 0 || t_out <= 0) return LR2_ERR_ARG;
+  if (!src || !dst || B <= 0 || t_in <= 0 || t_out <= 0 || row_elems == 0) return LR2_ERR_ARG;
   if (row_elems % 4 || src_bstride % 4 || src_tstride % 4) return LR2_ERR_SHAPE;
+  if (misaligned(src, 16) || misaligned(dst, 16)) return LR2_ERR_SHAPE;         // float4 loads and stores
   dim3 grid(grid_for(row_elems / 4, 64), B * t_out);
   LR2_LAUNCH(gather_rows_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const float*)src, index, (float*)dst,
                      t_in, t_out, row_elems, src_bstride, src_tstride);
@@ -868,8 +869,9 @@ extern "C" int lr2_gather_rows(const void* src, const int64_t* index, void* dst,
 
 extern "C" int lr2_gather_rows_bwd(const void* ddst, const int64_t* index, void* dsrc, int B, int t_in, int t_out,
                                    uint64_t row_elems, void* stream) {
-  if (!ddst || !dsrc || B <= 0 || t_in <= 0 || t_out <= 0) return LR2_ERR_ARG;
+  if (!ddst || !dsrc || B <= 0 || t_in <= 0 || t_out <= 0 || row_elems == 0) return LR2_ERR_ARG;
   if (row_elems % 4) return LR2_ERR_SHAPE;
+  if (misaligned(ddst, 16) || misaligned(dsrc, 16)) return LR2_ERR_SHAPE;       // float4 loads and stores
   dim3 grid(grid_for(row_elems / 4, 64), B * t_in);
   LR2_LAUNCH(gather_rows_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const float*)ddst, index,
                      (float*)dsrc, t_in, t_out, row_elems);
@@ -880,6 +882,8 @@ extern "C" int lr2_copy_rows(const void* src, void* dst, int dst_planes, uint64_
                              uint64_t dst_gstride, uint64_t dst_off, void* stream) {
   if (!src || !dst || rows <= 0 || D <= 0 || group <= 0) return LR2_ERR_ARG;
   if (D % 4 || dst_gstride % 4 || dst_off % 4) return LR2_ERR_SHAPE;
+  if (misaligned(src, 16)) return LR2_ERR_SHAPE;                                // float4 loads
+  if (dst_planes ? (misaligned(dst, 8) || dst_lo_off % 4) : misaligned(dst, 16)) return LR2_ERR_SHAPE;   // 4 x bf16 per plane / float4
   LR2_LAUNCH(copy_rows_kernel, dim3(grid_for((size_t)rows * D / 4)), dim3(256), 0, (hipStream_t)stream,
              (const float*)src, (float*)dst, dst_planes, (size_t)dst_lo_off, rows, D, group, dst_gstride, dst_off);
   CHECK_LAUNCH();
@@ -928,9 +932,11 @@ extern "C" int lr2_dropout_apply(const void* src, void* dst, uint64_t n, float d
 extern "C" int lr2_text_embed_bwd(const void* dx, const int64_t* sorted_ids, const int64_t* order, const int64_t* seg,
                                   void* dword, void* dseg, void* seg_partials, void* word_partials, int rows, int D,
                                   int64_t vocab, int n_seg, void* stream) {
-  if (!dx || !sorted_ids || !order || !seg || !dword || !dseg || !seg_partials || !word_partials || rows <= 0 || D <= 0)
+  if (!dx || !sorted_ids || !order || !seg || !dword || !dseg || !seg_partials || !word_partials || rows <= 0 || D <= 0 ||
+      vocab <= 0)
     return LR2_ERR_ARG;
   if (D % 4 || n_seg < 1 || n_seg > 4) return LR2_ERR_SHAPE;
+  if (misaligned(dx, 16) || misaligned(dword, 16) || misaligned(word_partials, 16)) return LR2_ERR_SHAPE;   // the word kernels' float4
   hipStream_t s = (hipStream_t)stream;
   LR2_LAUNCH(text_embed_bwd_word_kernel, dim3(rows), dim3(256), 0, s, (const float*)dx, sorted_ids, order, (float*)dword,
              (float*)word_partials, rows, D, vocab);
@@ -1120,8 +1126,10 @@ extern "C" int lr2_adamw_multi(const lr2_adamw_chunk* table_dev, int n_chunks, d
 extern "C" int lr2_text_embed(const int64_t* src, const int64_t* seg, const void* word, const void* pos,
                               const void* seg_table, void* out, int rows, int L, int D, int64_t vocab, int n_seg, int* err_flag,
                               void* stream) {
-  if (!src || !seg || !word || !pos || !seg_table || !out || rows <= 0 || L <= 0 || vocab <= 0 || n_seg <= 0) return LR2_ERR_ARG;
+  if (!src || !seg || !word || !pos || !seg_table || !out || rows <= 0 || L <= 0 || D <= 0 || vocab <= 0 || n_seg <= 0)
+    return LR2_ERR_ARG;
   if (D % 4) return LR2_ERR_SHAPE;
+  if (misaligned(word, 16) || misaligned(pos, 16) || misaligned(seg_table, 16) || misaligned(out, 16)) return LR2_ERR_SHAPE;   // float4
   LR2_LAUNCH(text_embed_kernel, dim3(grid_for((size_t)rows * D / 4)), dim3(256), 0, (hipStream_t)stream, src,
                      seg, (const float*)word, (const float*)pos, (const float*)seg_table, (float*)out, rows, L, D, vocab, n_seg,
                      err_flag);
@@ -1130,22 +1138,26 @@ extern "C" int lr2_text_embed(const int64_t* src, const int64_t* seg, const void
 
 extern "C" int lr2_patchify_planes(const void* img, int is_u8, void* out_hi, uint64_t lo_off, int ld, int B, int C, int H,
                                    int W, int ps, const float* mean3, const float* std3, void* stream) {
-  if (!img || !out_hi || B <= 0 || C <= 0 || ps <= 0) return LR2_ERR_ARG;
+  if (!img || !out_hi || B <= 0 || C <= 0 || H <= 0 || W <= 0 || ps <= 0) return LR2_ERR_ARG;
   const int Kd = C * ps * ps;
   if (H % ps || W % ps || C > 3 || (ps & 1) || ld < Kd || (ld & 3) || (lo_off & 1)) return LR2_ERR_SHAPE;
+  // what the kernel chosen below needs: the strip kernel reads uint4 / float4 (16 bytes) and writes 4 x bf16 per plane (8 bytes), the
+  // generic kernel reads single pixels and writes 4 x bf16 (VEC 4) or 2 x bf16 (VEC 2, 4 bytes) per plane
+  const bool strip = ps == 16 && ld == Kd && (lo_off & 3) == 0, vec4 = (ps & 3) == 0 && (lo_off & 3) == 0;
+  if ((strip && misaligned(img, 16)) || misaligned(out_hi, (strip || vec4) ? 8 : 4)) return LR2_ERR_SHAPE;
   const int normalize = (is_u8 && mean3 && std3) ? 1 : 0;
   const float m0 = normalize ? mean3[0] : 0.f, m1 = normalize && C > 1 ? mean3[1] : 0.f, m2 = normalize && C > 2 ? mean3[2] : 0.f;
   const float s0 = normalize ? std3[0] : 1.f, s1 = normalize && C > 1 ? std3[1] : 1.f, s2 = normalize && C > 2 ? std3[2] : 1.f;
   hipStream_t s = (hipStream_t)stream;
   bf16_t* o = (bf16_t*)out_hi;
-  if (ps == 16 && ld == Kd && (lo_off & 3) == 0) {    // ViT-B/16, ViT-L/16: the coalesced strip kernel
+  if (strip) {                                        // ViT-B/16, ViT-L/16: the coalesced strip kernel
     const dim3 grid(B * (H / ps));
     if (is_u8) LR2_LAUNCH(patchify_planes_kernel<true>, grid, dim3(256), 0, s, img, o, (size_t)lo_off, B, C, H, W, m0, m1, m2, s0, s1, s2, normalize);
     else LR2_LAUNCH(patchify_planes_kernel<false>, grid, dim3(256), 0, s, img, o, (size_t)lo_off, B, C, H, W, m0, m1, m2, s0, s1, s2, 0);
     CHECK_LAUNCH();
   }
   const size_t P = (size_t)(H / ps) * (W / ps);
-  if ((ps & 3) == 0 && (lo_off & 3) == 0) {
+  if (vec4) {
     const dim3 grid(grid_for((size_t)B * P * (ld / 4)));
     if (is_u8) LR2_LAUNCH((patchify_planes_generic_kernel<true, 4>), grid, dim3(256), 0, s, img, o, (size_t)lo_off, B, C, H, W, ps, ld, m0, m1, m2, s0, s1, s2, normalize);
     else LR2_LAUNCH((patchify_planes_generic_kernel<false, 4>), grid, dim3(256), 0, s, img, o, (size_t)lo_off, B, C, H, W, ps, ld, m0, m1, m2, s0, s1, s2, 0);
@@ -1166,7 +1178,7 @@ extern "C" int lr2_ndcg(const void* scores, const int64_t* gold, const int64_t* 
 }
 
 extern "C" int lr2_patchify(const void* img, void* out, int B, int C, int H, int W, int ps, void* stream) {
-  if (!img || !out || B <= 0 || C <= 0 || ps <= 0) return LR2_ERR_ARG;
+  if (!img || !out || B <= 0 || C <= 0 || H <= 0 || W <= 0 || ps <= 0) return LR2_ERR_ARG;
   if (H % ps || W % ps) return LR2_ERR_SHAPE;
   LR2_LAUNCH(patchify_kernel, dim3(grid_for((size_t)B * C * H * W)), dim3(256), 0, (hipStream_t)stream,
                      (const float*)img, (float*)out, B, C, H, W, ps);
@@ -1175,8 +1187,9 @@ extern "C" int lr2_patchify(const void* img, void* out, int B, int C, int H, int
 
 extern "C" int lr2_vit_assemble(const void* patch_proj, const void* cls, const void* pos, void* out, int B, int P, int D,
                                 void* stream) {
-  if (!patch_proj || !cls || !pos || !out || B <= 0 || P <= 0) return LR2_ERR_ARG;
+  if (!patch_proj || !cls || !pos || !out || B <= 0 || P <= 0 || D <= 0) return LR2_ERR_ARG;
   if (D % 4) return LR2_ERR_SHAPE;
+  if (misaligned(patch_proj, 16) || misaligned(cls, 16) || misaligned(pos, 16) || misaligned(out, 16)) return LR2_ERR_SHAPE;   // float4
   LR2_LAUNCH(vit_assemble_kernel, dim3(grid_for((size_t)B * (P + 1) * D / 4)), dim3(256), 0, (hipStream_t)stream,
                      (const float*)patch_proj, (const float*)cls, (const float*)pos, (float*)out, B, P, D);
   CHECK_LAUNCH();

@@ -991,6 +991,7 @@ def self_attn_plan(batch: int, heads: int, L: int, ld: Optional[int] = None, ld_
 
 
 def gather_rows(src, index, dst, *, B, t_in, t_out, row_elems, src_bstride=None, src_tstride=None):
+    """dst[b, j] = src[b, clamp(index[b, j])]; index None: j.  An index outside [0, t_in) is clamped into it (lr2_gather_rows)."""
     _chk_f32(src, dst)
     if index is not None and index.dtype != torch.int64:
         raise TypeError("index must be int64")
@@ -1001,6 +1002,7 @@ def gather_rows(src, index, dst, *, B, t_in, t_out, row_elems, src_bstride=None,
 
 
 def gather_rows_bwd(ddst, index, dsrc, *, B, t_in, t_out, row_elems):
+    """dsrc[b, t] = sum of ddst[b, j] over the j whose clamped index is t (the forward's clamp): every row of dsrc is overwritten."""
     _chk_f32(ddst, dsrc)
     _nat.check(_nat.lib().lr2_gather_rows_bwd(ddst.data_ptr(), _ptr(index), dsrc.data_ptr(), B, t_in, t_out, row_elems,
                                         _stream()), "lr2_gather_rows_bwd")
