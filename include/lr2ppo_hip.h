@@ -214,6 +214,22 @@ int lr2_xattn_fwd(const void* Q, const void* K, const void* V, void* O, int o_pl
 int lr2_xattn_bwd(const void* Q, const void* K, const void* V, const void* dO, void* dQ, void* dK, void* dV,
                   int planes, uint64_t q_lo_off, uint64_t kv_lo_off, int batch, int heads, int Lq, int Lk, int head_dim,
                   float post_scale, void* stream);
+/* The wide form of the pair above, for more than 16 image tokens (--max_imgs up to 64): the argument lists, formulas, fp32 FMA
+ * arithmetic, output forms and alignment rules of lr2_xattn_fwd / lr2_xattn_bwd with 1 <= Lk <= 64 (K / V of one (sequence, head) stay
+ * resident in LDS, 48 KiB at 64 keys: the reason for the limit).  No atomics, every sum in a fixed order: two calls give the same bits.
+ * At Lk <= 16 the results meet the narrow pair's bounds but are not bit-equal to it (the backward adds in another order).
+ * LR2_ERR_ARG: a NULL pointer, batch or heads not positive.  LR2_ERR_SHAPE: Lq outside [1, 256], Lk outside [1, 64], head_dim outside
+ * [4, 96] or % 4, a pointer or plane offset off the narrow pair's alignment.  A refused call launches nothing.
+ * replaces: finetune/xit.py:133-146 at max_imgs > 16 (the reference accepts any number of image tokens). */
+int lr2_xattn_fwd_wide(const void* Q, const void* K, const void* V, void* O, int o_planes, uint64_t o_lo_off, int batch,
+                       int heads, int Lq, int Lk, int head_dim, float post_scale, void* stream);
+int lr2_xattn_bwd_wide(const void* Q, const void* K, const void* V, const void* dO, void* dQ, void* dK, void* dV,
+                       int planes, uint64_t q_lo_off, uint64_t kv_lo_off, int batch, int heads, int Lq, int Lk, int head_dim,
+                       float post_scale, void* stream);
+/* Diagnostic: counts[0] = accepted lr2_xattn_fwd_wide calls, counts[1] = accepted lr2_xattn_bwd_wide calls (host counters, not
+ * synchronised; a refused call moves neither).
+ * replaces: nothing (a test hook, as lr2_gemm_f16_launch_counts: which form a dispatch ran). */
+int lr2_xattn_wide_launch_counts(uint64_t counts[2]);
 
 /* TencentPretrain self-attention core, per (sequence, head): S = Q K^T * scale + (seg[key]>0 ? 0 : -10000),
  * P = softmax(S), O = P V -- both products on the matrix cores (split-bf16 x3), softmax in fp32.

@@ -15,8 +15,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 LIB_PATH = os.path.join(CSRC, "liblr2ppo_hip.so")
-SOURCES = ["gemm.hip", "gemm256.hip", "gemm256_mx.hip", "gemm256_b1.hip", "gemm256_f16.hip", "gemm256_tn_b1.hip", "norm.hip", "attn.hip", "selfattn_fwd.hip", "selfattn_bwd.hip", "first_token_attn.hip", "selfattn_mx.hip", "selfattn_mx_blocked.hip","selfattn_b1_train.hip", "selfattn_b1_blocked.hip", "misc.hip", "fp8.hip", "fp8_train.hip"]
+SOURCES = ["gemm.hip", "gemm256.hip", "gemm256_mx.hip", "gemm256_b1.hip", "gemm256_f16.hip", "gemm256_tn_b1.hip", "norm.hip", "attn.hip", "attn_wide.hip", "selfattn_fwd.hip", "selfattn_bwd.hip", "first_token_attn.hip", "selfattn_mx.hip", "selfattn_mx_blocked.hip","selfattn_b1_train.hip", "selfattn_b1_blocked.hip", "misc.hip", "fp8.hip", "fp8_train.hip"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "gemm256_ring.h"), os.path.join(CSRC, "fp8_common.h"), os.path.join(CSRC, "selfattn_common.h"), os.path.join(CSRC, "selfattn_b1.h"), os.path.join(INCLUDE, "lr2ppo_hip.h")]
+# flags of single sources, after the common ones (each is explained at the top of its file)
+EXTRA_FLAGS = {"attn_wide.hip": ["-fno-slp-vectorize"]}
 
 ABI_VERSION = 27     # == LR2_ABI_VERSION of include/lr2ppo_hip.h (tests assert the two agree)
 
@@ -51,7 +53,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     procs = []
     for s in SOURCES:
         obj = os.path.join(CSRC, s.replace(".hip", ".o"))
-        cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", INCLUDE, "-I", CSRC, "-c",
+        cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", *EXTRA_FLAGS.get(s, []), "-I", INCLUDE, "-I", CSRC, "-c",
                os.path.join(CSRC, s), "-o", obj]
         if verbose:
             print(" ".join(cmd))
@@ -113,6 +115,9 @@ SIGNATURES = {
     "lr2_colsum": [_P, _I, _U64, _I, _I, _I, _P, _I, _P, _P],
     "lr2_xattn_fwd": [_P, _P, _P, _P, _I, _U64, _I, _I, _I, _I, _I, _F, _P],
     "lr2_xattn_bwd": [_P, _P, _P, _P, _P, _P, _P, _I, _U64, _U64, _I, _I, _I, _I, _I, _F, _P],
+    "lr2_xattn_fwd_wide": [_P, _P, _P, _P, _I, _U64, _I, _I, _I, _I, _I, _F, _P],
+    "lr2_xattn_bwd_wide": [_P, _P, _P, _P, _P, _P, _P, _I, _U64, _U64, _I, _I, _I, _I, _I, _F, _P],
+    "lr2_xattn_wide_launch_counts": [C.POINTER(C.c_uint64)],
     "lr2_self_attn_fwd": [_P, _P, _P, _U64, _I, _P, _P, _P, _U64, _I, _P, _F, _U64, _U32, _I, _I, _I, _I, _F, _P],
     "lr2_first_token_attn": [_P, _I, _P, _P, _U64, _I, _P, _P, _I, _I, _I, _I, _I, _F, _P],
     "lr2_self_attn_bwd": [_P, _P, _P, _U64, _I, _P, _U64, _I, _P, _P, _P, _P, _U64, _I, _P, _U64, _I, _P, _P, _F, _U64, _U32, _I,

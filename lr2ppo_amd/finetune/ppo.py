@@ -172,6 +172,7 @@ class _Head(nn.Module):
             self.seq_length, self.max_imgs = args.seq_length, args.max_imgs
             if self.seq_length != SEQ_LEN:
                 raise ValueError("seq_length must be 196 (hard-coded in the reference, finetune/ppo.py:219-220)")
+            ops.check_max_imgs(self.max_imgs)       # 1 .. 64 image tokens: the XiT cross-attention kernels' range
             self.text_proj = Mlp(FEAT, FEAT * 4, FEAT, nn.GELU, 0)
             self.img_proj = Mlp(FEAT, FEAT * 4, FEAT, nn.GELU, 0)
         if self.has_tail:

@@ -890,25 +890,51 @@ def colsum(x, out, partials, *, rows, cols, ld=None, nblocks=128):
     return out
 
 
-def xattn_fwd(q, k, v, o, *, batch, heads, Lq, Lk, head_dim, post_scale):
-    """o: fp32 tensor or Planes."""
+XATTN_NARROW_LK = 16     # keys of the 16-key XiT attention pair (csrc/attn.hip)
+XATTN_MAX_LK = 64        # ... of the wide pair (csrc/attn_wide.hip: K / V of one (sequence, head) resident in LDS) = the largest max_imgs
+
+
+def check_max_imgs(max_imgs):
+    """The heads' limit in words, at construction: the XiT cross-attention serves 1 .. XATTN_MAX_LK image tokens."""
+    if not 1 <= int(max_imgs) <= XATTN_MAX_LK:
+        raise ValueError(f"max_imgs = {max_imgs}: the XiT cross-attention kernels serve 1 to {XATTN_MAX_LK} image tokens "
+                         f"(K / V of one sequence and head stay resident in LDS)")
+
+
+def _xattn_wide(Lk, wide):
+    """Which form runs: the 16-key pair up to 16 keys (its results keep their bits), the wide pair for 17 .. 64 or when forced."""
+    if Lk > XATTN_MAX_LK:
+        raise ValueError(f"XiT attention: Lk = {Lk} keys, the kernels serve at most {XATTN_MAX_LK} (for the heads: --max_imgs <= {XATTN_MAX_LK})")
+    return bool(wide) or Lk > XATTN_NARROW_LK
+
+
+def xattn_fwd(q, k, v, o, *, batch, heads, Lq, Lk, head_dim, post_scale, wide=False):
+    """o: fp32 tensor or Planes.  wide=True forces the wide kernel at any Lk <= 64 (tests compare the two forms at Lk <= 16)."""
+    name = "lr2_xattn_fwd_wide" if _xattn_wide(Lk, wide) else "lr2_xattn_fwd"      # raises at Lk > 64, before anything else
     o_pl = isinstance(o, Planes)
     _chk_f32(q, k, v, None if o_pl else o)
-    _nat.check(_nat.lib().lr2_xattn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), 1 if o_pl else 0,
-                                        o.lo_off if o_pl else 0, batch, heads, Lq, Lk, head_dim, post_scale, _stream()),
-               "lr2_xattn_fwd")
+    _nat.check(getattr(_nat.lib(), name)(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), 1 if o_pl else 0,
+                                         o.lo_off if o_pl else 0, batch, heads, Lq, Lk, head_dim, post_scale, _stream()), name)
     return o
 
 
-def xattn_bwd(q, k, v, do, dq, dk, dv, *, batch, heads, Lq, Lk, head_dim, post_scale):
-    """dq / dk / dv: all fp32 tensors or all Planes."""
+def xattn_bwd(q, k, v, do, dq, dk, dv, *, batch, heads, Lq, Lk, head_dim, post_scale, wide=False):
+    """dq / dk / dv: all fp32 tensors or all Planes.  wide: as xattn_fwd."""
+    name = "lr2_xattn_bwd_wide" if _xattn_wide(Lk, wide) else "lr2_xattn_bwd"
     pl = isinstance(dq, Planes)
     _chk_f32(q, k, v, do)
     if not pl:
         _chk_f32(dq, dk, dv)
-    _nat.check(_nat.lib().lr2_xattn_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), do.data_ptr(), dq.data_ptr(), dk.data_ptr(),
-                                        dv.data_ptr(), 1 if pl else 0, dq.lo_off if pl else 0, dk.lo_off if pl else 0, batch,
-                                        heads, Lq, Lk, head_dim, post_scale, _stream()), "lr2_xattn_bwd")
+    _nat.check(getattr(_nat.lib(), name)(q.data_ptr(), k.data_ptr(), v.data_ptr(), do.data_ptr(), dq.data_ptr(), dk.data_ptr(),
+                                         dv.data_ptr(), 1 if pl else 0, dq.lo_off if pl else 0, dk.lo_off if pl else 0, batch,
+                                         heads, Lq, Lk, head_dim, post_scale, _stream()), name)
+
+
+def xattn_wide_launch_counts():
+    """(forward, backward) calls the wide XiT attention pair has accepted (a test hook: which form a dispatch ran)."""
+    c = (C.c_uint64 * 2)()
+    _nat.check(_nat.lib().lr2_xattn_wide_launch_counts(c), "lr2_xattn_wide_launch_counts")
+    return int(c[0]), int(c[1])
 
 
 def _qkv_ptrs(qkv, E):
