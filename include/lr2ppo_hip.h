@@ -355,8 +355,70 @@ typedef struct lr2_adamw_chunk {
 int lr2_adamw_multi(const lr2_adamw_chunk* table_dev, int n_chunks, double lr, double beta1, double beta2,
                     double eps, const void* lr_dev, void* stream);
 /* lr_dev (may be NULL): device float read by the kernel in place of `lr` -- a captured HIP graph of a training step then follows
- * the scheduler without re-capture.
- *
+ * the scheduler without re-capture. */
+
+/* Added within ABI 27 (purely additive: no signature or struct changes).  Multi-tensor Adafactor with an external learning rate
+ * (relative_step=False, scale_parameter=False, beta1=None -- what every launcher passes), fp32, for 2-D (factored second moment)
+ * and 1-D tensors.  A 2-D tensor [rows, cols] is cut into tiles of LR2_ADAFACTOR_TILE_ROWS x LR2_ADAFACTOR_TILE_COLS (row-major tile
+ * order: index = row_tile * n_col_tiles + col_tile); a 1-D tensor (rows == 0) into chunks of LR2_ADAFACTOR_CHUNK_1D elements.
+ * One call issues LR2_ADAFACTOR_LAUNCHES kernel launches whatever the number of tensors (one fewer, no finalise, when n_fin == 0):
+ *   1 stats     (grid n_tiles): u = g*g + eps0; per tile the row sums and column sums of u -> workspace partials (fp32, summed in
+ *               fp64).  1-D chunks: v = beta2t v + (1-beta2t) u, U = g rsqrt(v), sum U^2 -> the chunk's partial.
+ *   2 finalise  (grid n_fin): per tensor the partials summed in tile order (fp64), row = beta2t row + (1-beta2t) mean_j(u),
+ *               col likewise with mean_i(u); the rows entry of a tensor also stores mean(row).
+ *   3 update^2  (grid n_tiles): U = g * rsqrt(row / mean(row))[i] * rsqrt(col)[j]; sum U^2 per tile -> partial (fp64).
+ *   4 apply     (grid n_tiles): rms = sqrt(sum of the tensor's partials in tile order / numel); U /= max(1, rms / clip_threshold);
+ *               U *= lr; p += (-weight_decay*lr) * p; p -= U.
+ * No atomics: every sum has a fixed order, results are bit-reproducible.  Nothing returns to the host.  p / g / the state vectors
+ * need 4-byte alignment only: 16-byte accesses are used for a tensor whose pointers are 16-byte aligned and whose cols % 4 == 0,
+ * element accesses otherwise.  Offsets are 64-bit throughout.
+ * HBM traffic of a 2-D tensor: g three times, p once in and once out = 20 B per parameter. */
+#define LR2_ADAFACTOR_TILE_ROWS 512
+#define LR2_ADAFACTOR_TILE_COLS 1024
+#define LR2_ADAFACTOR_CHUNK_1D 8192
+#define LR2_ADAFACTOR_FIN_COLS 1024 /* columns per finalise entry of kind 1 */
+#define LR2_ADAFACTOR_LAUNCHES 4
+typedef struct lr2_adafactor_tensor {
+  void* p;
+  const void* g;
+  void* row;        /* 2-D: exp_avg_sq_row [rows]; 1-D: exp_avg_sq [cols] */
+  void* col;        /* 2-D: exp_avg_sq_col [cols]; 1-D: unused */
+  uint64_t rows;    /* 0: a 1-D tensor of `cols` elements */
+  uint64_t cols;
+  uint64_t ws_row;  /* BYTE offsets into the workspace: fp32 row partials [n_col_tiles][rows] */
+  uint64_t ws_col;  /* fp32 column partials [n_row_tiles][cols] */
+  uint64_t ws_mean; /* fp32 mean(row) */
+  uint64_t ws_sq;   /* fp64 sum-of-U^2 partials [n_tiles], 8-byte aligned */
+  uint32_t n_tiles; /* tiles (2-D) or chunks (1-D) of this tensor */
+  uint32_t n_col_tiles;
+  uint32_t n_row_tiles;
+  uint32_t _pad;
+  double weight_decay;
+} lr2_adafactor_tensor;
+typedef struct lr2_adafactor_tile {
+  uint32_t tensor; /* index into the tensor table */
+  uint32_t index;  /* tile / chunk number within that tensor */
+} lr2_adafactor_tile;
+typedef struct lr2_adafactor_fin {
+  uint32_t tensor;
+  uint32_t kind;  /* 0: all rows of the tensor (one entry per 2-D tensor); 1: LR2_ADAFACTOR_FIN_COLS columns from `start` */
+  uint64_t start;
+} lr2_adafactor_fin;
+/* tensors / tiles / fin: DEVICE tables (every tile of every tensor exactly once; one kind-0 entry and ceil(cols / FIN_COLS) kind-1
+ * entries per 2-D tensor; n_fin may be 0 when every tensor is 1-D).  ws: DEVICE workspace the offsets point into, 8-byte aligned.
+ * beta2t = 1 - step^decay_rate, eps0 and clip_threshold by value (formed in double on the host, like the reference's math.pow);
+ * lr as lr2_adamw_multi's (lr_dev, may be NULL: device float read in its place).
+ * replaces: tencentpretrain/utils/optimizers.py:518-603 (Adafactor.step) for relative_step=False, scale_parameter=False,
+ * beta1=None. */
+int lr2_adafactor_multi(const lr2_adafactor_tensor* tensors_dev, const lr2_adafactor_tile* tiles_dev, int n_tiles,
+                        const lr2_adafactor_fin* fin_dev, int n_fin, void* ws_dev, double lr, double beta2t, double eps0,
+                        double clip_threshold, const void* lr_dev, void* stream);
+/* Diagnostic: counts[0] = accepted lr2_adafactor_multi calls, counts[1] = kernel launches they issued (host counters, not
+ * synchronised; a refused call moves neither).
+ * replaces: nothing (a test hook, as lr2_xattn_wide_launch_counts). */
+int lr2_adafactor_launch_counts(uint64_t counts[2]);
+
+/*
  * The per-step scalars such a graph reads -- dst_dev[0..7] = seed (uint64, the dropout seed of lr2_epilogue.drop_seed_dev /
  * lr2_layernorm_bwd), dst_dev[8 + 4 i ..] = lrs[i] (float, i < n_lrs <= 14) -- are written by ONE small kernel whose arguments
  * carry the values: no host buffer has to outlive the call, so steps can be enqueued ahead of the device. */

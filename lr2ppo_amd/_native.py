@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 LIB_PATH = os.path.join(CSRC, "liblr2ppo_hip.so")
-SOURCES = ["gemm.hip", "gemm256.hip", "gemm256_mx.hip", "gemm256_b1.hip", "gemm256_f16.hip", "gemm256_tn_b1.hip", "norm.hip", "attn.hip", "attn_wide.hip", "selfattn_fwd.hip", "selfattn_bwd.hip", "first_token_attn.hip", "selfattn_mx.hip", "selfattn_mx_blocked.hip","selfattn_b1_train.hip", "selfattn_b1_blocked.hip", "misc.hip", "fp8.hip", "fp8_train.hip"]
+SOURCES = ["gemm.hip", "gemm256.hip", "gemm256_mx.hip", "gemm256_b1.hip", "gemm256_f16.hip", "gemm256_tn_b1.hip", "norm.hip", "attn.hip", "attn_wide.hip", "selfattn_fwd.hip", "selfattn_bwd.hip", "first_token_attn.hip", "selfattn_mx.hip", "selfattn_mx_blocked.hip","selfattn_b1_train.hip", "selfattn_b1_blocked.hip", "misc.hip", "adafactor.hip", "fp8.hip", "fp8_train.hip"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "gemm256_ring.h"), os.path.join(CSRC, "fp8_common.h"), os.path.join(CSRC, "selfattn_common.h"), os.path.join(CSRC, "selfattn_b1.h"), os.path.join(INCLUDE, "lr2ppo_hip.h")]
 # flags of single sources, after the common ones (each is explained at the top of its file)
 EXTRA_FLAGS = {"attn_wide.hip": ["-fno-slp-vectorize"]}
@@ -90,6 +90,25 @@ class AdamChunk(C.Structure):
                 ("weight_decay", C.c_float), ("_pad", C.c_float)]
 
 
+# tables of lr2_adafactor_multi (include/lr2ppo_hip.h); the tile sizes are the header's LR2_ADAFACTOR_* (tests hold them together)
+ADAFACTOR_TILE_ROWS, ADAFACTOR_TILE_COLS, ADAFACTOR_CHUNK_1D, ADAFACTOR_FIN_COLS, ADAFACTOR_LAUNCHES = 512, 1024, 8192, 1024, 4
+
+
+class AdafactorTensor(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("row", C.c_void_p), ("col", C.c_void_p), ("rows", C.c_uint64),
+                ("cols", C.c_uint64), ("ws_row", C.c_uint64), ("ws_col", C.c_uint64), ("ws_mean", C.c_uint64), ("ws_sq", C.c_uint64),
+                ("n_tiles", C.c_uint32), ("n_col_tiles", C.c_uint32), ("n_row_tiles", C.c_uint32), ("_pad", C.c_uint32),
+                ("weight_decay", C.c_double)]
+
+
+class AdafactorTile(C.Structure):
+    _fields_ = [("tensor", C.c_uint32), ("index", C.c_uint32)]
+
+
+class AdafactorFin(C.Structure):
+    _fields_ = [("tensor", C.c_uint32), ("kind", C.c_uint32), ("start", C.c_uint64)]
+
+
 _P, _I, _F, _U64, _U32 = C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_uint32
 
 # name -> argtypes; every symbol include/lr2ppo_hip.h declares must appear here (tests check both ways)
@@ -136,6 +155,8 @@ SIGNATURES = {
     "lr2_nll_loss": [_P, _P, _I, _I, _P, _P, _P],
     "lr2_pair_hinge": [_P, _I, _F, _P, _P, _P],
     "lr2_adamw_multi": [_P, _I, C.c_double, C.c_double, C.c_double, C.c_double, _P, _P],
+    "lr2_adafactor_multi": [_P, _P, _I, _P, _I, _P, C.c_double, C.c_double, C.c_double, C.c_double, _P, _P],
+    "lr2_adafactor_launch_counts": [C.POINTER(C.c_uint64)],
     "lr2_step_scalars_store": [_P, _U64, _P, _I, _P],
     "lr2_quant_mxfp8": [_P, _I, _P, _P, _I, _I, _P],
     "lr2_layernorm_fwd_mxfp8": [_P, _P, _P, _P, _P, _P, _I, _I, _F, _I, _P],

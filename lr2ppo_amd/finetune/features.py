@@ -604,6 +604,10 @@ def build_encoder_optimizer(args, fx: FeatureExtractor):
     bias / gamma / beta: finetune/ppo.py:381-393, the rule of every TencentPretrain fine-tuning script) -> (optimizer, scheduler)."""
     from ..tencentpretrain.utils.optimizers import str2optimizer, str2scheduler
     from .ppo import _grouped
+    if args.optimizer != "adamw":
+        raise NotImplementedError(f"build_encoder_optimizer: optimizer {args.optimizer!r} cannot fine-tune the encoders -- the ViT patch "
+                                  "projection is a 4-D parameter, which Adafactor's factored second moment (a torch.mm of a row and a "
+                                  "column vector in the reference) cannot step; use adamw")
     opt = str2optimizer[args.optimizer](_grouped(list(fx.named_parameters())), lr=args.learning_rate, correct_bias=False)
     if args.scheduler == "constant":
         sch = str2scheduler[args.scheduler](opt)

@@ -40,7 +40,7 @@ from ..tencentpretrain.model_saver import save_model
 from ..tencentpretrain.opts import adv_opts, finetune_opts, tokenizer_opts
 from ..tencentpretrain.utils.config import load_hyperparam
 from ..tencentpretrain.utils.logging import init_logger
-from ..tencentpretrain.utils.optimizers import str2optimizer, str2scheduler
+from ..tencentpretrain.utils.optimizers import Adafactor, str2optimizer, str2scheduler
 from . import misc
 from .xit import XiT
 
@@ -677,12 +677,17 @@ def _grouped(named):
 
 
 def build_optimizer(args, model):
-    if args.optimizer not in str2optimizer:
-        raise NotImplementedError(f"optimizer {args.optimizer!r}: only adamw is on the HIP path (every LR2PPO launcher uses it)")
-    optimizer = str2optimizer[args.optimizer](_grouped(list(model.actor.named_parameters())), lr=args.learning_rate,
-                                              correct_bias=False)
-    critic_optimizer = str2optimizer[args.optimizer](_grouped(list(model.critic.named_parameters())),
-                                                     lr=args.critic_learning_rate, correct_bias=False)
+    """finetune/ppo.py:379-419."""
+    if args.optimizer in ["adamw"]:
+        optimizer = str2optimizer[args.optimizer](_grouped(list(model.actor.named_parameters())), lr=args.learning_rate,
+                                                  correct_bias=False)
+        critic_optimizer = str2optimizer[args.optimizer](_grouped(list(model.critic.named_parameters())),
+                                                         lr=args.critic_learning_rate, correct_bias=False)
+    else:
+        optimizer = str2optimizer[args.optimizer](_grouped(list(model.actor.named_parameters())), lr=args.learning_rate,
+                                                  scale_parameter=False, relative_step=False)
+        critic_optimizer = str2optimizer[args.optimizer](_grouped(list(model.critic.named_parameters())),
+                                                         lr=args.critic_learning_rate, scale_parameter=False, relative_step=False)
     if args.scheduler in ["constant"]:
         scheduler = str2scheduler[args.scheduler](optimizer)
         critic_scheduler = str2scheduler[args.scheduler](critic_optimizer)
@@ -933,6 +938,9 @@ class GraphedPPOStep:
             raise NotImplementedError("GraphedPPOStep: the data-parallel step can be captured with the RCCL ('nccl') backend only "
                                       f"(backend {dp.backend!r} stages its collectives through the host)")
         for o in (optimizer, critic_optim):
+            if isinstance(o, Adafactor):
+                raise NotImplementedError("GraphedPPOStep: Adafactor cannot be captured -- beta2t = 1 - step^decay_rate changes every "
+                                          "step and travels to the kernels by value, a graph would freeze it; step eagerly")
             if not hasattr(o, "use_device_lr"):
                 raise TypeError("GraphedPPOStep needs lr2ppo_amd's AdamW (device-resident learning rates)")
         self.args, self.model, self.reward_model, self.opt, self.copt = args, model, reward_model, optimizer, critic_optim

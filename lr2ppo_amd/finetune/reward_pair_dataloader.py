@@ -160,10 +160,12 @@ def load_or_initialize_parameters(args, model):
 
 def build_optimizer(args, model):
     """reward_pair_dataloader.py:321-344."""
-    if args.optimizer not in str2optimizer:
-        raise NotImplementedError(f"optimizer {args.optimizer!r}: only adamw is on the HIP path (every LR2PPO launcher uses it)")
-    optimizer = str2optimizer[args.optimizer](_grouped(list(model.named_parameters())), lr=args.learning_rate,
-                                              correct_bias=False)
+    if args.optimizer in ["adamw"]:
+        optimizer = str2optimizer[args.optimizer](_grouped(list(model.named_parameters())), lr=args.learning_rate,
+                                                  correct_bias=False)
+    else:
+        optimizer = str2optimizer[args.optimizer](_grouped(list(model.named_parameters())), lr=args.learning_rate,
+                                                  scale_parameter=False, relative_step=False)
     if args.scheduler in ["constant"]:
         scheduler = str2scheduler[args.scheduler](optimizer)
     elif args.scheduler in ["constant_with_warmup"]:

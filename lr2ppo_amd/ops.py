@@ -1146,6 +1146,24 @@ def adamw_multi(table_dev: torch.Tensor, n_chunks: int, lr: float, beta1: float,
                                               lr_dev.data_ptr() if lr_dev is not None else None, _stream()), "lr2_adamw_multi")
 
 
+def adafactor_multi(tensors_dev: torch.Tensor, tiles_dev: torch.Tensor, n_tiles: int, fin_dev: Optional[torch.Tensor], n_fin: int,
+                    ws_dev: torch.Tensor, lr: float, beta2t: float, eps0: float, clip_threshold: float, n_params: int = 0,
+                    n_bytes: float = 0.0, lr_dev: Optional[torch.Tensor] = None):
+    """One Adafactor step over the tensors of the device tables (lr2_adafactor_multi: _native.ADAFACTOR_LAUNCHES launches whatever
+    their number).  n_bytes: the HBM traffic the caller counted (20 B per element of a 2-D tensor, 28 B of a 1-D one)."""
+    with _Timed(f"adafactor_{n_params}", 0.0, n_bytes):
+        _nat.check(_nat.lib().lr2_adafactor_multi(tensors_dev.data_ptr(), tiles_dev.data_ptr(), n_tiles, _ptr(fin_dev), n_fin,
+                                                  ws_dev.data_ptr(), lr, beta2t, eps0, clip_threshold,
+                                                  lr_dev.data_ptr() if lr_dev is not None else None, _stream()), "lr2_adafactor_multi")
+
+
+def adafactor_launch_counts():
+    """(accepted lr2_adafactor_multi calls, kernel launches they issued) since the library was loaded (a test hook)."""
+    c = (C.c_uint64 * 2)()
+    _nat.check(_nat.lib().lr2_adafactor_launch_counts(c), "lr2_adafactor_launch_counts")
+    return int(c[0]), int(c[1])
+
+
 class Mx8:
     """A matrix in MX-FP8 (OCP MX v1.0: e4m3fn bytes + one E8M0 scale byte per 32 consecutive elements of a row) -- the operand
     format of gemm_mxfp8, the inference-only fp8 fast mode (csrc/fp8.hip; NOT the parity path)."""

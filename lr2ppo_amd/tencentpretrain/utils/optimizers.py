@@ -1,4 +1,4 @@
-"""AdamW + LR schedules with the TencentPretrain call signatures, stepping on one fused HIP kernel.
+"""AdamW, Adafactor + LR schedules with the TencentPretrain call signatures, stepping on table-driven HIP kernels.
 
 Drop-in for the symbols finetune/ppo.py uses from tencentpretrain/utils/optimizers.py of the reference:
 `AdamW(params, lr, betas, eps, weight_decay, correct_bias)` (:305-402), `get_linear_schedule_with_warmup`
@@ -6,7 +6,8 @@ Drop-in for the symbols finetune/ppo.py uses from tencentpretrain/utils/optimize
 The update is the reference's exactly (eps 1e-6 outside the sqrt, optional bias correction folded into the
 step size, decoupled decay applied AFTER the Adam update with the same lr) but runs as ONE launch per
 parameter group over a device-resident chunk table instead of ~5 small kernels per tensor.
-Adafactor and the other schedules of the reference are out of scope (no LR2PPO launcher uses them).
+`Adafactor` (:405-603) steps on lr2_adafactor_multi (four launches per group) for the arguments every launcher passes
+(relative_step=False, scale_parameter=False, beta1=None); the eight schedules of `str2scheduler` are the reference's (:29-302).
 """
 from __future__ import annotations
 
@@ -150,6 +151,177 @@ class AdamW(Optimizer):
         return loss
 
 
+def adafactor_plan(shapes):
+    """The tables of one lr2_adafactor_multi call for tensors of these shapes (1-D or 2-D), as plain Python:
+    -> (per-tensor dicts, tiles [(tensor, index)], fin [(tensor, kind, start)], workspace bytes).
+    A 2-D tensor is cut into TILE_ROWS x TILE_COLS tiles in row-major tile order, a 1-D one into CHUNK_1D chunks.  The workspace
+    holds, per tensor, one fp64 sum-of-U^2 partial per tile (all of these first: 8-byte aligned), and per 2-D tensor the fp32 row
+    partials [col tiles][rows], the fp32 column partials [row tiles][cols] and mean(row).  Offsets are in bytes."""
+    TR, TC, CH, FC = (_native.ADAFACTOR_TILE_ROWS, _native.ADAFACTOR_TILE_COLS, _native.ADAFACTOR_CHUNK_1D,
+                      _native.ADAFACTOR_FIN_COLS)
+    tensors, tiles, fin = [], [], []
+    off = 0
+    for ti, shape in enumerate(shapes):
+        if len(shape) == 2:
+            rows, cols = shape
+            n_rt, n_ct = -(-rows // TR), -(-cols // TC)
+            n = n_rt * n_ct
+        elif len(shape) == 1:
+            rows, cols, n_rt, n_ct = 0, shape[0], 0, 0
+            n = -(-cols // CH)
+        else:
+            raise NotImplementedError(f"Adafactor steps 1-D and 2-D parameters, got shape {tuple(shape)}")
+        if cols < 1 or (len(shape) == 2 and rows < 1):
+            raise ValueError(f"Adafactor: empty parameter of shape {tuple(shape)}")
+        tensors.append(dict(rows=rows, cols=cols, n_tiles=n, n_row_tiles=n_rt, n_col_tiles=n_ct, ws_sq=off, ws_row=0, ws_col=0,
+                            ws_mean=0))
+        off += 8 * n
+        tiles += [(ti, i) for i in range(n)]
+        if rows:
+            fin.append((ti, 0, 0))
+            fin += [(ti, 1, s) for s in range(0, cols, FC)]
+    for t in tensors:
+        if t["rows"]:
+            t["ws_row"] = off
+            off += 4 * t["n_col_tiles"] * t["rows"]
+            t["ws_col"] = off
+            off += 4 * t["n_row_tiles"] * t["cols"]
+            t["ws_mean"] = off
+            off += 4
+    return tensors, tiles, fin, off
+
+
+class Adafactor(Optimizer):
+    """The reference's Adafactor (tencentpretrain/utils/optimizers.py:405-603; constructor signature, defaults and state keys are
+    its own) stepping on lr2_adafactor_multi: four launches per param group whatever the number of tensors, no host
+    synchronisation.  The device path serves what every launcher passes -- an external learning rate without a first moment:
+    relative_step=False, scale_parameter=False, beta1=None -- and 1-D / 2-D parameters; anything else raises at construction.
+    State per parameter: `step`, `exp_avg_sq_row` [R] / `exp_avg_sq_col` [C] (2-D) or `exp_avg_sq` (1-D), and `RMS`.  `RMS` is
+    kept for the layout of a reference-written state only and holds 0: the reference reads it under scale_parameter=True alone.
+    There is no external_update: the heads' step functions then take the unfused out_layer.fc1 route on their own."""
+
+    def __init__(self, params, lr=None, eps=(1e-30, 1e-3), clip_threshold=1.0, decay_rate=-0.8, beta1=None, weight_decay=0.0,
+                 scale_parameter=True, relative_step=True, warmup_init=False):
+        if lr is not None and relative_step:
+            raise ValueError("Cannot combine manual lr and relative_step options")
+        if warmup_init and not relative_step:
+            raise ValueError("warmup_init requires relative_step=True")
+        if relative_step or scale_parameter or beta1 is not None:
+            raise NotImplementedError("lr2ppo_amd Adafactor serves relative_step=False, scale_parameter=False, beta1=None with an "
+                                      "external lr (what every LR2PPO launcher passes); got "
+                                      f"relative_step={relative_step}, scale_parameter={scale_parameter}, beta1={beta1}")
+        if lr is None:
+            raise NotImplementedError("lr2ppo_amd Adafactor needs an external lr (relative_step=False)")
+        super().__init__(params, dict(lr=lr, eps=eps, clip_threshold=clip_threshold, decay_rate=decay_rate, beta1=beta1,
+                                      weight_decay=weight_decay, scale_parameter=scale_parameter, relative_step=relative_step,
+                                      warmup_init=warmup_init))
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.dim() not in (1, 2):
+                    raise NotImplementedError(f"lr2ppo_amd Adafactor steps 1-D and 2-D parameters, got shape {tuple(p.shape)} "
+                                              "(the reference's _approx_sq_grad is a torch.mm and cannot step it either)")
+        self._tables = {}
+
+    def _ensure_state(self, p):
+        st = self.state[p]
+        if len(st) == 0:
+            st["step"] = 0
+            if p.dim() == 2:
+                st["exp_avg_sq_row"] = torch.zeros(p.shape[0], dtype=torch.float32, device=p.device)
+                st["exp_avg_sq_col"] = torch.zeros(p.shape[1], dtype=torch.float32, device=p.device)
+            else:
+                st["exp_avg_sq"] = torch.zeros_like(p.data)
+            st["RMS"] = 0
+        return st
+
+    def _moments(self, p):
+        st = self._ensure_state(p)
+        ms = (st["exp_avg_sq_row"], st["exp_avg_sq_col"]) if p.dim() == 2 else (st["exp_avg_sq"],)
+        want = ((p.shape[0],), (p.shape[1],)) if p.dim() == 2 else (tuple(p.shape),)
+        for m, w in zip(ms, want):
+            if m.dtype != torch.float32 or m.device != p.device or not m.is_contiguous() or tuple(m.shape) != w:
+                raise RuntimeError("lr2ppo_amd Adafactor needs contiguous float32 HIP state tensors of the parameter's row / column shape")
+        return ms
+
+    MAX_TABLES = 8      # cached (tables, workspace) entries; the oldest goes first
+
+    def _table(self, gi: int, group, ps):
+        """Device tables and workspace of one call over `ps`, cached per (group, set of parameters) with the raw pointers as the
+        entry's signature.  As with AdamW._tables, a pointer that changes -- zero_grad(set_to_none=True) followed by a freshly
+        allocated gradient, load_state_dict -- rebuilds the entry, and the rebuild is a blocking host-to-device copy of pageable
+        memory inside step(): keep gradients in place (bind_grads does) to stay asynchronous.  Every entry owns a workspace (5.9 MB
+        for a head), so at most MAX_TABLES are kept: a group whose skip pattern varies (pointwise_2data_trad: two patterns) stays
+        within that."""
+        # the tables hold raw pointers: parameters, gradients AND the state vectors (load_state_dict replaces the latter)
+        sig = tuple((p.data_ptr(), p.grad.data_ptr(), tuple(p.shape), group["weight_decay"]) + tuple(m.data_ptr() for m in self._moments(p))
+                    for p in ps)
+        key = (gi,) + tuple(id(p) for p in ps)
+        cached = self._tables.get(key)
+        if cached is not None and cached[0] == sig:
+            return cached[1]
+        tensors, tiles, fin, ws_bytes = adafactor_plan([tuple(p.shape) for p in ps])
+        dev = ps[0].device
+        tarr = (_native.AdafactorTensor * len(ps))()
+        n_bytes = 0.0
+        for i, (p, t) in enumerate(zip(ps, tensors)):
+            ms = self._moments(p)
+            a = tarr[i]
+            a.p, a.g, a.row, a.col = p.data_ptr(), p.grad.data_ptr(), ms[0].data_ptr(), ms[1].data_ptr() if len(ms) == 2 else None
+            a.rows, a.cols, a.n_tiles, a.n_col_tiles, a.n_row_tiles = t["rows"], t["cols"], t["n_tiles"], t["n_col_tiles"], t["n_row_tiles"]
+            a.ws_row, a.ws_col, a.ws_mean, a.ws_sq = t["ws_row"], t["ws_col"], t["ws_mean"], t["ws_sq"]
+            a.weight_decay = group["weight_decay"]
+            n_bytes += (20.0 if t["rows"] else 28.0) * p.numel()
+        larr = (_native.AdafactorTile * len(tiles))()
+        for i, (ti, idx) in enumerate(tiles):
+            larr[i].tensor, larr[i].index = ti, idx
+        farr = (_native.AdafactorFin * max(1, len(fin)))()
+        for i, (ti, kind, start) in enumerate(fin):
+            farr[i].tensor, farr[i].kind, farr[i].start = ti, kind, start
+        up = lambda arr: torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)      # noqa: E731
+        entry = dict(tensors=up(tarr), tiles=up(larr), n_tiles=len(tiles), fin=up(farr) if fin else None, n_fin=len(fin),
+                     ws=torch.empty((ws_bytes + 7) // 8, dtype=torch.float64, device=dev), n_params=sum(p.numel() for p in ps),
+                     n_bytes=n_bytes)
+        self._tables.pop(key, None)
+        while len(self._tables) >= self.MAX_TABLES:
+            self._tables.pop(next(iter(self._tables)))
+        self._tables[key] = (sig, entry)
+        return entry
+
+    @torch.no_grad()
+    def step(self, closure: Callable = None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        # everything is checked before any launch and before any step count moves: a refusal leaves the optimizer as it was
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                if p.grad.is_sparse:
+                    raise RuntimeError("Adafactor does not support sparse gradients.")
+                if p.dtype != torch.float32 or not p.is_cuda or not p.is_contiguous() or not p.grad.is_contiguous() \
+                        or p.grad.dtype != torch.float32:
+                    raise RuntimeError("lr2ppo_amd AdamW needs contiguous float32 HIP parameters and gradients")
+                self._moments(p)
+        for gi, group in enumerate(self.param_groups):
+            ps = [p for p in group["params"] if p.grad is not None]      # a parameter without a gradient is skipped: no step, no decay
+            # beta2t = 1 - step^decay_rate travels by value, one per call: parameters that skipped steps (pointwise_2data_trad's
+            # unused projection) go in a call of their own, so a group costs ADAFACTOR_LAUNCHES launches per distinct step count
+            by_step = {}
+            for p in ps:
+                st = self._ensure_state(p)
+                st["step"] += 1
+                by_step.setdefault(st["step"], []).append(p)
+            for t, sub in by_step.items():
+                e = self._table(gi, group, sub)
+                beta2t = 1.0 - math.pow(t, group["decay_rate"])
+                ops.adafactor_multi(e["tensors"], e["tiles"], e["n_tiles"], e["fin"], e["n_fin"], e["ws"], group["lr"], beta2t,
+                                    group["eps"][0], group["clip_threshold"], n_params=e["n_params"], n_bytes=e["n_bytes"])
+            ops.mark_params_written(ps)
+        return loss
+
+
 def get_constant_schedule(optimizer, last_epoch=-1):
     return LambdaLR(optimizer, lambda _: 1, last_epoch=last_epoch)
 
@@ -173,6 +345,99 @@ def get_linear_schedule_with_warmup(optimizer, num_warmup_steps, num_training_st
     return LambdaLR(optimizer, lr_lambda, last_epoch)
 
 
-str2optimizer = {"adamw": AdamW}
-str2scheduler = {"linear": get_linear_schedule_with_warmup, "constant": get_constant_schedule,
-                 "constant_with_warmup": get_constant_schedule_with_warmup}
+# The five schedules below give the reference's multipliers (tests/golden/sched_all.json to 1e-12: the same floating-point
+# operations in the same order) behind its signatures and defaults (optimizers.py:89-302); the text is this project's.
+def _ramp(step, warm):
+    """Share of a linear warm-up from 0 that `step` has covered."""
+    return float(step) / float(max(1, warm))
+
+
+def _after_warmup(step, warm, total):
+    """Share of the steps between the warm-up's end and `total` that `step` has covered."""
+    return float(step - warm) / float(max(1, total - warm))
+
+
+def get_tri_stage_schedule(optimizer, num_warmup_steps, num_decay_steps, num_training_steps, init_lr_scale=0.01, final_lr_scale=0.05,
+                           last_epoch=-1):
+    """Three stages (arXiv 1904.08779): a linear rise from init_lr_scale to 1 over the warm-up, 1 until num_decay_steps before the
+    end, then an exponential fall that reaches final_lr_scale at num_training_steps and stays there."""
+    peak = optimizer.defaults["lr"]
+    first, last = peak * init_lr_scale, peak * final_lr_scale
+    fall_from = num_training_steps - num_decay_steps
+
+    def multiplier(step):
+        if step < num_warmup_steps:
+            per_step = (peak - first) / num_warmup_steps
+            return (first + step * per_step) / peak
+        if step < fall_from:
+            return 1
+        if step > num_training_steps:
+            return last / peak
+        rate = -math.log(final_lr_scale) / max(num_decay_steps, 1)
+        return math.exp(-rate * (step - num_training_steps + num_decay_steps))
+    return LambdaLR(optimizer, multiplier, last_epoch)
+
+
+def get_cosine_schedule_with_warmup(optimizer, num_warmup_steps, num_training_steps, num_cycles=0.5, last_epoch=-1):
+    """Linear warm-up from 0, then num_cycles periods of a cosine between 1 and 0 (the default half period ends at 0)."""
+    def multiplier(step):
+        if step < num_warmup_steps:
+            return _ramp(step, num_warmup_steps)
+        angle = math.pi * float(num_cycles) * 2.0 * _after_warmup(step, num_warmup_steps, num_training_steps)
+        return max(0.0, 0.5 * (1.0 + math.cos(angle)))
+    return LambdaLR(optimizer, multiplier, last_epoch)
+
+
+def get_cosine_with_hard_restarts_schedule_with_warmup(optimizer, num_warmup_steps, num_training_steps, num_cycles=1, last_epoch=-1):
+    """Linear warm-up from 0, then num_cycles half cosines from 1 to 0, each starting again at 1; 0 from num_training_steps on."""
+    def multiplier(step):
+        if step < num_warmup_steps:
+            return _ramp(step, num_warmup_steps)
+        done = _after_warmup(step, num_warmup_steps, num_training_steps)
+        if done >= 1.0:
+            return 0.0
+        within_cycle = (float(num_cycles) * done) % 1.0
+        return max(0.0, 0.5 * (1.0 + math.cos(math.pi * within_cycle)))
+    return LambdaLR(optimizer, multiplier, last_epoch)
+
+
+def get_polynomial_decay_schedule_with_warmup(optimizer, num_warmup_steps, num_training_steps, lr_end=1e-7, power=1.0, last_epoch=-1):
+    """Linear warm-up from 0, then (share of the decay steps left) ** power between the optimizer's lr and lr_end; lr_end past
+    num_training_steps.  The multiplier is the target rate over the optimizer's lr."""
+    top = optimizer.defaults["lr"]
+    if not top > lr_end:
+        raise AssertionError(f"polynomial schedule: lr_end {lr_end} is not below the optimizer's lr {top}")
+
+    def multiplier(step):
+        if step < num_warmup_steps:
+            return _ramp(step, num_warmup_steps)
+        if step > num_training_steps:
+            return lr_end / top
+        left = 1 - (step - num_warmup_steps) / (num_training_steps - num_warmup_steps)
+        return ((top - lr_end) * left ** power + lr_end) / top
+    return LambdaLR(optimizer, multiplier, last_epoch)
+
+
+def get_inverse_square_root_schedule_with_warmup(optimizer, num_warmup_steps, num_training_steps, warmup_init_lr=0.0, last_epoch=-1):
+    """Linear warm-up from warmup_init_lr to the optimizer's lr, then lr * sqrt(num_warmup_steps / step); a rate of 1e-7 past
+    num_training_steps."""
+    top = optimizer.defaults["lr"]
+    if not top > warmup_init_lr:
+        raise AssertionError(f"inverse-sqrt schedule: warmup_init_lr {warmup_init_lr} is not below the optimizer's lr {top}")
+
+    def multiplier(step):
+        if step < num_warmup_steps:
+            per_step = (top - warmup_init_lr) / num_warmup_steps
+            return (warmup_init_lr + step * per_step) / top
+        if step > num_training_steps:
+            return 1e-7 / top
+        return (top * num_warmup_steps ** 0.5 * step ** -0.5) / top
+    return LambdaLR(optimizer, multiplier, last_epoch)
+
+
+str2optimizer = {"adamw": AdamW, "adafactor": Adafactor}
+str2scheduler = {"linear": get_linear_schedule_with_warmup, "cosine": get_cosine_schedule_with_warmup,
+                 "cosine_with_restarts": get_cosine_with_hard_restarts_schedule_with_warmup,
+                 "polynomial": get_polynomial_decay_schedule_with_warmup, "constant": get_constant_schedule,
+                 "constant_with_warmup": get_constant_schedule_with_warmup,
+                 "inverse_sqrt": get_inverse_square_root_schedule_with_warmup, "tri_stage": get_tri_stage_schedule}
