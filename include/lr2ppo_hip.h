@@ -48,7 +48,12 @@ typedef struct lr2_epilogue {
   float alpha;
   float drop_p;       /* 0 disables dropout */
   uint32_t drop_site;
-  uint32_t _pad;
+  /* Global gradient-norm clipping of the fused optimizer step (adam_p): when non-NULL the result g[m,n] is multiplied by
+   * *adam_gscale_dev (device float, the coefficient lr2_clip_coef writes) as ONE fp32 multiply of its own before the AdamW update --
+   * the bits of lr2_adamw_multi_scaled on the materialised gradient.  NULL: the unscaled update, as before.  The pointer lies in
+   * what used to be 8 bytes of padding in front of drop_seed (a uint32 _pad and the compiler's fill; zero in every caller that
+   * zeroes the struct): sizeof and every other offset are unchanged. */
+  const void* adam_gscale_dev;
   uint64_t drop_seed;
   /* Fused optimizer step (weight-gradient GEMMs): when adam_p is set the result g[m,n] (after alpha) is not stored but
    * consumed by the AdamW update of lr2_adamw_multi on (adam_p, adam_m, adam_v)[m, ld_out*m + n]; `out` may be NULL.
@@ -356,6 +361,31 @@ int lr2_adamw_multi(const lr2_adamw_chunk* table_dev, int n_chunks, double lr, d
                     double eps, const void* lr_dev, void* stream);
 /* lr_dev (may be NULL): device float read by the kernel in place of `lr` -- a captured HIP graph of a training step then follows
  * the scheduler without re-capture. */
+
+/* Global gradient-norm clipping (added within ABI 27: new entry points; lr2_epilogue.adam_gscale_dev took the place of padding).
+ * The rule is torch.nn.utils.clip_grad_norm_ with norm_type = 2 and error_if_nonfinite = False:
+ *   total_norm = sqrt(sum of g^2 over every gradient), coef = min(1, max_norm / (total_norm + 1e-6)), g <- g * coef.
+ * Everything stays on the device; every sum has a fixed order (a thread's elements in index order, lane tree, waves in index
+ * order -- no atomics), so results are bit-reproducible.  Four pieces:
+ *   lr2_clip_sumsq    partials[i] = sum over chunk i of g^2, fp64 (squares formed and added in fp64), one workgroup per chunk of the
+ *                     table lr2_adamw_multi reads (only g and count are used).  16-byte loads for a chunk whose g is 16-byte
+ *                     aligned, element loads otherwise.
+ *   lr2_clip_gram_dot *slot = factor * sum_ij A[i,j] * B[i,j] of two fp32 [n, n] matrices (rows ld_a / ld_b floats apart), fp64, one
+ *                     workgroup.  With A = dY dY^T and B = X X^T this is the squared Frobenius norm of dW = alpha dY^T X
+ *                     (factor = alpha^2) -- the gradient of out_layer.fc1.weight, which the fused update never materialises.
+ *   lr2_clip_coef     one workgroup adds slots[0..n) in index order (fp64) and writes out[0] = total_norm, out[1] = coef as fp32,
+ *                     both formed in fp64 and rounded once.  A NaN sum gives NaN, NaN; an infinite one gives inf, 0.
+ *   lr2_adamw_multi_scaled   lr2_adamw_multi on g * *gscale_dev (device float; one fp32 multiply of its own, then the same update):
+ *                     gradients in memory stay unscaled.  16-byte accesses for a chunk whose four pointers are 16-byte aligned,
+ *                     element accesses otherwise.
+ * LR2_ERR_ARG: a NULL pointer (lr_dev excepted), n_chunks / n <= 0, ld < n, a partials / slot pointer that is not 8-byte aligned,
+ * an out / gscale_dev pointer that is not 4-byte aligned, max_norm < 0 or NaN.
+ * replaces: nothing in the reference (it has no clip); torch.nn.utils.clip_grad_norm_ is what a user of it would call. */
+int lr2_clip_sumsq(const lr2_adamw_chunk* table_dev, int n_chunks, void* partials_dev, void* stream);
+int lr2_clip_gram_dot(const void* A, const void* B, int n, int ld_a, int ld_b, double factor, void* slot_dev, void* stream);
+int lr2_clip_coef(const void* slots_dev, int n, double max_norm, void* out_dev, void* stream);
+int lr2_adamw_multi_scaled(const lr2_adamw_chunk* table_dev, int n_chunks, double lr, double beta1, double beta2, double eps,
+                           const void* lr_dev, const void* gscale_dev, void* stream);
 
 /* Added within ABI 27 (purely additive: no signature or struct changes).  Multi-tensor Adafactor with an external learning rate
  * (relative_step=False, scale_parameter=False, beta1=None -- what every launcher passes), fp32, for 2-D (factored second moment)

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 LIB_PATH = os.path.join(CSRC, "liblr2ppo_hip.so")
-SOURCES = ["gemm.hip", "gemm256.hip", "gemm256_mx.hip", "gemm256_b1.hip", "gemm256_f16.hip", "gemm256_tn_b1.hip", "norm.hip", "attn.hip", "attn_wide.hip", "selfattn_fwd.hip", "selfattn_bwd.hip", "first_token_attn.hip", "selfattn_mx.hip", "selfattn_mx_blocked.hip","selfattn_b1_train.hip", "selfattn_b1_blocked.hip", "misc.hip", "adafactor.hip", "fp8.hip", "fp8_train.hip"]
+SOURCES = ["gemm.hip", "gemm256.hip", "gemm256_mx.hip", "gemm256_b1.hip", "gemm256_f16.hip", "gemm256_tn_b1.hip", "norm.hip", "attn.hip", "attn_wide.hip", "selfattn_fwd.hip", "selfattn_bwd.hip", "first_token_attn.hip", "selfattn_mx.hip", "selfattn_mx_blocked.hip","selfattn_b1_train.hip", "selfattn_b1_blocked.hip", "misc.hip", "adafactor.hip", "clip.hip", "fp8.hip", "fp8_train.hip"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "gemm256_ring.h"), os.path.join(CSRC, "fp8_common.h"), os.path.join(CSRC, "selfattn_common.h"), os.path.join(CSRC, "selfattn_b1.h"), os.path.join(INCLUDE, "lr2ppo_hip.h")]
 # flags of single sources, after the common ones (each is explained at the top of its file)
 EXTRA_FLAGS = {"attn_wide.hip": ["-fno-slp-vectorize"]}
@@ -75,7 +75,7 @@ class Epilogue(C.Structure):
                 ("out_z", C.c_void_p), ("out_hi", C.c_void_p), ("out_lo_off", C.c_uint64), ("ld_planes", C.c_int32),
                 ("ld_resid", C.c_int32), ("ld_aux", C.c_int32), ("ld_out", C.c_int32),
                 ("ld_z", C.c_int32), ("act", C.c_int32), ("accumulate", C.c_int32), ("alpha", C.c_float),
-                ("drop_p", C.c_float), ("drop_site", C.c_uint32), ("_pad", C.c_uint32), ("drop_seed", C.c_uint64),
+                ("drop_p", C.c_float), ("drop_site", C.c_uint32), ("adam_gscale_dev", C.c_void_p), ("drop_seed", C.c_uint64),
                 ("adam_p", C.c_void_p), ("adam_m", C.c_void_p), ("adam_v", C.c_void_p), ("adam_lr", C.c_double),
                 ("adam_beta1", C.c_double), ("adam_beta2", C.c_double), ("adam_eps", C.c_double),
                 ("adam_weight_decay", C.c_double), ("colsum", C.c_void_p), ("colsum_ws", C.c_void_p), ("drop_seed_dev", C.c_void_p), ("adam_lr_dev", C.c_void_p)]
@@ -155,6 +155,10 @@ SIGNATURES = {
     "lr2_nll_loss": [_P, _P, _I, _I, _P, _P, _P],
     "lr2_pair_hinge": [_P, _I, _F, _P, _P, _P],
     "lr2_adamw_multi": [_P, _I, C.c_double, C.c_double, C.c_double, C.c_double, _P, _P],
+    "lr2_clip_sumsq": [_P, _I, _P, _P],
+    "lr2_clip_gram_dot": [_P, _P, _I, _I, _I, C.c_double, _P, _P],
+    "lr2_clip_coef": [_P, _I, C.c_double, _P, _P],
+    "lr2_adamw_multi_scaled": [_P, _I, C.c_double, C.c_double, C.c_double, C.c_double, _P, _P, _P],
     "lr2_adafactor_multi": [_P, _P, _I, _P, _I, _P, C.c_double, C.c_double, C.c_double, C.c_double, _P, _P],
     "lr2_adafactor_launch_counts": [C.POINTER(C.c_uint64)],
     "lr2_step_scalars_store": [_P, _U64, _P, _I, _P],

@@ -231,6 +231,10 @@ struct Epilogue {
   uint32_t seed_dev : 1;     // dev_scalar is the device-resident dropout seed (graph capture, see dropout_key_of)
   uint32_t lr_dev : 1;       // dev_scalar is the device-resident learning rate of the fused AdamW step
   uint32_t store_nt : 1;     // result stores (out / out_z / planes) non-temporal: large outputs that the next kernel streams from HBM anyway
+  uint32_t gscale : 1;       // fused AdamW step under gradient-norm clipping: the result is multiplied by the device float that aux_z
+                             // points to (lr2_epilogue.adam_gscale_dev) before the update.  The pointer travels in aux_z -- free in such
+                             // a launch (act == 2 is refused with it) -- because dev_scalar already carries the rate and a pointer of
+                             // its own cost the 8-wave kernel, which runs at its 128-VGPR / 104-SGPR limits, 28 spilled VGPRs
   float alpha;
   float drop_scale;      // 1/(1-p) or 0 when dropout is off
   uint32_t drop_thr;     // bits 0-15: threshold; bits 16-31: the site id when the seed is device-resident

@@ -632,6 +632,10 @@ Epilogue to_device_epilogue(const lr2_epilogue* e) {
     d.adam_ob2 = (float)(1.0 - e->adam_beta2);
     d.adam_eps = (float)e->adam_eps;
     d.adam_wd = (float)e->adam_weight_decay;
+    if (e->adam_gscale_dev) {        // the coefficient's pointer rides in aux_z (common.h::Epilogue::gscale)
+      d.aux_z = (const float*)e->adam_gscale_dev;
+      d.gscale = 1;
+    }
   }
   return d;
 }
@@ -694,6 +698,8 @@ extern "C" int lr2_gemm(const void* A, const void* B, int M, int N, int K, int l
                         void* stream) {
   if (!A || !B || M <= 0 || N <= 0 || K <= 0 || !epi || (!epi->out && !epi->out_hi && !epi->adam_p)) return LR2_ERR_ARG;
   if (epi->adam_p && (!epi->adam_m || !epi->adam_v || epi->out || epi->out_hi || epi->ld_out % 4)) return LR2_ERR_ARG;
+  // the clip coefficient scales the fused step only, and travels in the device epilogue's aux_z
+  if (epi->adam_gscale_dev && (!epi->adam_p || epi->act == 2 || epi->aux_z || misaligned(epi->adam_gscale_dev, 4))) return LR2_ERR_ARG;
   if (passes != 1 && passes != 3) return LR2_ERR_ARG;
   if (trans_a && !trans_b) return LR2_ERR_ARG;   // (1,0) is not a form the path needs (refused here, before a launch is counted)
   if (epi->act < 0 || epi->act > 2 || (epi->act == 2 && !epi->aux_z)) return LR2_ERR_ARG;   // GELU' needs its input

@@ -162,6 +162,10 @@ __device__ __forceinline__ void epilogue_apply4(const Epilogue& e, float4 v, flo
     const size_t off = (size_t)m * e.ld_out + n;
     float4 p = L.s[0], mm = L.s[SR], vv = L.s[SO];
 const float adam_lr = e.lr_dev ? scalar_load_f32((const float*)e.dev_scalar) : e.adam_lr;
+    if (e.gscale) {           // gradient-norm clipping: g * coef, a rounding of its own (contraction is off), as lr2_adamw_multi_scaled
+      const float coef = scalar_load_f32(e.aux_z);
+      v.x *= coef; v.y *= coef; v.z *= coef; v.w *= coef;
+    }
         adam_update(p.x, v.x, mm.x, vv.x, adam_lr, e.adam_b1, e.adam_b2, e.adam_ob1, e.adam_ob2, e.adam_eps, e.adam_wd);
     adam_update(p.y, v.y, mm.y, vv.y, adam_lr, e.adam_b1, e.adam_b2, e.adam_ob1, e.adam_ob2, e.adam_eps, e.adam_wd);
     adam_update(p.z, v.z, mm.z, vv.z, adam_lr, e.adam_b1, e.adam_b2, e.adam_ob1, e.adam_ob2, e.adam_eps, e.adam_wd);

@@ -440,7 +440,8 @@ def trunk_forward(ws: Workspace, P, W, text, img, bs: int, tags: int, n_img: int
 
 
 def trunk_backward(ws: Workspace, P, W, G, text, img, dg2, bs, tags, n_img, E, *, drop: Optional[DropCfg] = None,
-                   img_shared: bool = False, dp=None, fc1_update=None, fc1_early: bool = False, input_grads: bool = False):
+                   img_shared: bool = False, dp=None, fc1_update=None, fc1_early: bool = False, input_grads: bool = False,
+                   fc1_defer: Optional[list] = None):
     """Backward of trunk_forward(save=True); fills G[...] for every trunk parameter.  dg2: fp32 [bs*tags, E].
     input_grads: also return (d text [bs*tags*196, E], d img [Mi_src, E]) as fresh fp32 tensors -- the gradients the
     reference's autograd hands to whatever produced text_emb / img_emb (encoders being fine-tuned behind the head:
@@ -452,7 +453,10 @@ def trunk_backward(ws: Workspace, P, W, G, text, img, dg2, bs, tags, n_img, E, *
     fc1_early: issue that fused update right behind the input-gradient GEMM instead of at the very end -- same operands, same
     bits; a model whose backward runs on a second stream uses it so that its 12-GB HBM-bound pass falls beside the other
     model's MFMA-bound token GEMMs instead of beside the other model's own 12-GB pass (single-rank only: with data
-    parallelism the update waits for the factor all-gather and stays last)."""
+    parallelism the update waits for the factor all-gather and stays last).
+    fc1_defer (a list, with fc1_update): gradient-norm clipping -- the fused update may not run before the clip coefficient exists, so
+    it is not issued here; (apply, dzo_all, flat_all, K, alpha) is appended instead: the factors of dW = alpha dzo_all^T flat_all
+    [K rows each; the gathered ones under data parallelism] for fc1_grad_sumsq, and apply() to issue the update afterwards."""
     N = bs * tags
     Mt, F = N * SEQ_LEN, 4 * E
     Mi_src = (bs if img_shared else N) * n_img
@@ -490,7 +494,7 @@ def trunk_backward(ws: Workspace, P, W, G, text, img, dg2, bs, tags, n_img, E, *
         ops.gemm(dzo_all, flat_all, None if fc1_update is not None else G[FC1], F, Wflat, Kall, trans_a=True, trans_b=True,
                  lda=F, ldb=Wflat, splitk_ws=skw, splits=sp, block_m=bm, alpha=alpha, adam=fc1_update)
 
-    early = fc1_early and fc1_update is not None and fc1_pending is None
+    early = fc1_early and fc1_update is not None and fc1_pending is None and fc1_defer is None
     if early:
         fused_fc1_update(dzo, flat, N, 1.0)
     # image part of the concat -> dense [Mi, E] gradient
@@ -530,10 +534,28 @@ def trunk_backward(ws: Workspace, P, W, G, text, img, dg2, bs, tags, n_img, E, *
     if (fc1_pending is not None or fc1_update is not None) and not early:
         if fc1_pending is not None:
             dzo_all, flat_all = dp.gather_planes_finish(fc1_pending[0]), dp.gather_planes_finish(fc1_pending[1])
-            fused_fc1_update(dzo_all, flat_all, N * dp.world, 1.0 / dp.world)            # already the rank average
+            last = (dzo_all, flat_all, N * dp.world, 1.0 / dp.world)                     # already the rank average
         else:
-            fused_fc1_update(dzo, flat, N, 1.0)
+            last = (dzo, flat, N, 1.0)
+        if fc1_defer is not None and fc1_update is not None:
+            fc1_defer.append((lambda: fused_fc1_update(*last),) + last)
+        else:
+            fused_fc1_update(*last)
     return d_text, d_img
+
+
+def fc1_grad_sumsq(ws: Workspace, dzo_all: Planes, flat_all: Planes, K: int, alpha: float, slot: torch.Tensor):
+    """slot[0] (float64) = ||alpha dzo_all^T flat_all||_F^2, the squared norm of the out_layer.fc1.weight gradient the fused update
+    never writes, from its two thin factors [K, 3072] and [K, (196 + max_imgs) * 768]:
+        ||dW||_F^2 = alpha^2 sum_ij (dzo dzo^T)_ij (flat flat^T)_ij
+    -- two K x K Gram products on the NT GEMM (always split-bf16 x 3, whatever ops.set_gemm_passes says: the norm is compared with
+    fp32 sums) and one fixed-order fp64 reduction (ops.clip_gram_dot).  Reads the factors once (~85 MB) instead of a 2 GB gradient.
+    K % 4 == 0 (the GEMM's column rule)."""
+    ga, gb = ws.mat("clip_gram_a", K, K), ws.mat("clip_gram_b", K, K)
+    for src, dst in ((dzo_all, ga), (flat_all, gb)):
+        skw, sp, bm = _splitk_ws(ws, K, K, src.cols)
+        ops.gemm(src, src, dst, K, K, src.cols, splitk_ws=skw, splits=sp, block_m=bm, passes=3)
+    ops.clip_gram_dot(ga, gb, slot, n=K, factor=alpha * alpha)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -602,13 +602,14 @@ class ExtractingLoader:
 def build_encoder_optimizer(args, fx: FeatureExtractor):
     """AdamW + schedule over the two encoder stacks with the reference's grouping (weight decay 0.01 except names containing
     bias / gamma / beta: finetune/ppo.py:381-393, the rule of every TencentPretrain fine-tuning script) -> (optimizer, scheduler)."""
-    from ..tencentpretrain.utils.optimizers import str2optimizer, str2scheduler
+    from ..tencentpretrain.utils.optimizers import apply_grad_clip, str2optimizer, str2scheduler
     from .ppo import _grouped
     if args.optimizer != "adamw":
         raise NotImplementedError(f"build_encoder_optimizer: optimizer {args.optimizer!r} cannot fine-tune the encoders -- the ViT patch "
                                   "projection is a 4-D parameter, which Adafactor's factored second moment (a torch.mm of a row and a "
                                   "column vector in the reference) cannot step; use adamw")
     opt = str2optimizer[args.optimizer](_grouped(list(fx.named_parameters())), lr=args.learning_rate, correct_bias=False)
+    apply_grad_clip(args, opt)
     if args.scheduler == "constant":
         sch = str2scheduler[args.scheduler](opt)
     elif args.scheduler == "constant_with_warmup":
@@ -640,7 +641,9 @@ def finetune_pointwise_step(args, fx: FeatureExtractor, model, optimizer, schedu
     else:
         ops.smooth_l1(logits.view(-1), tgts.to(device=dev, dtype=torch.float32).contiguous().view(-1), loss, dlogits.view(-1),
                       n=logits.numel(), beta=0.3)
-    fuse = getattr(args, "fuse_fc1_update", True) and hasattr(optimizer, "external_update")
+    # (gradient-norm clipping takes the unfused route here: the gradient is materialised and sits in the optimizer's table)
+    fuse = getattr(args, "fuse_fc1_update", True) and hasattr(optimizer, "external_update") \
+        and getattr(optimizer, "max_grad_norm", None) is None
     fa = optimizer.external_update(model.out_layer.fc1.weight) if fuse else None
     d_text, d_img = model.engine_backward(dlogits, dp, fc1_update=fa, input_grads=True)
     wh = dp.reduce_start(model)                      # the head's tail all-reduce overlaps the encoder backward

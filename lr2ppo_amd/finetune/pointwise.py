@@ -26,7 +26,7 @@ from ..tencentpretrain.model_saver import save_model
 from ..tencentpretrain.opts import adv_opts, finetune_opts, tokenizer_opts
 from ..tencentpretrain.utils.config import load_hyperparam
 from ..tencentpretrain.utils.logging import init_logger
-from ..tencentpretrain.utils.optimizers import str2optimizer, str2scheduler
+from ..tencentpretrain.utils.optimizers import apply_grad_clip, str2optimizer, str2scheduler
 from . import misc
 from .ppo import FEAT, SEQ_LEN, Actor, Mlp, SyntheticMovieNet, _DataParallel, _grouped, _init_normal  # noqa: F401
 
@@ -129,6 +129,7 @@ def build_optimizer(args, model):
     else:
         optimizer = str2optimizer[args.optimizer](_grouped(list(model.named_parameters())), lr=args.learning_rate,
                                                   scale_parameter=False, relative_step=False)
+    apply_grad_clip(args, optimizer)
     if args.scheduler in ["constant"]:
         scheduler = str2scheduler[args.scheduler](optimizer)
     elif args.scheduler in ["constant_with_warmup"]:
@@ -153,7 +154,9 @@ def train_model(args, model, optimizer, scheduler, text_emb_batch, img_emb_batch
     else:
         target = tgts_batch.to(device=dev, dtype=torch.float32).contiguous().view(-1)
         ops.smooth_l1(logits.view(-1), target, loss, dlogits.view(-1), n=logits.numel(), beta=0.3)
-    fuse = getattr(args, "fuse_fc1_update", True) and hasattr(optimizer, "external_update")
+    # (gradient-norm clipping takes the unfused route here: the gradient is materialised and sits in the optimizer's table)
+    fuse = getattr(args, "fuse_fc1_update", True) and hasattr(optimizer, "external_update") \
+        and getattr(optimizer, "max_grad_norm", None) is None
     fa = optimizer.external_update(model.out_layer.fc1.weight) if fuse else None
     model.engine_backward(dlogits, dp, fc1_update=fa)
     dp.finish(dp.reduce_start(model))
@@ -231,6 +234,8 @@ def build_parser():
     parser.add_argument("--synthetic_items", type=int, default=0, help="use SyntheticMovieNet with this many train items")
     parser.add_argument("--synthetic_val_items", type=int, default=16)
     parser.add_argument("--max_steps", type=int, default=0, help="stop after this many training steps (0 = run all epochs)")
+    parser.add_argument("--max_grad_norm", type=float, default=0.0,
+                        help="clip the global L2 norm of each optimizer's gradients to this value on the device (0 = off; adamw only)")
     # the composed model (encoder(embedding(src, seg), seg) -> head: tencentpretrain/models/model.py:32-41 upstream).  The reference's
     # launcher already carries --pretrained_model_path / --vit_pretrained_model_path for the RoBERTa and ViT checkpoints but loads them
     # into a module that holds only the head (pointwise.py:239-271); with --raw_inputs they load into the two encoder stacks that run

@@ -19,7 +19,7 @@ from torch.utils.data import DataLoader, Dataset
 from torch.utils.data.distributed import DistributedSampler
 
 from .. import engine, ops, runtime
-from ..tencentpretrain.utils.optimizers import str2optimizer, str2scheduler
+from ..tencentpretrain.utils.optimizers import apply_grad_clip, str2optimizer, str2scheduler
 from .letor import QueryRows
 from .ppo import FEAT, Mlp, _grouped, _init_normal
 from .xit import XiT
@@ -145,6 +145,7 @@ def build_optimizer(args, model):
     else:
         optimizer = str2optimizer[args.optimizer](_grouped(list(model.named_parameters())), lr=args.learning_rate,
                                                   scale_parameter=False, relative_step=False)
+    apply_grad_clip(args, optimizer)
     if args.scheduler in ["constant"]:
         scheduler = str2scheduler[args.scheduler](optimizer)
     elif args.scheduler in ["constant_with_warmup"]:

@@ -40,7 +40,7 @@ from ..tencentpretrain.model_saver import save_model
 from ..tencentpretrain.opts import adv_opts, finetune_opts, tokenizer_opts
 from ..tencentpretrain.utils.config import load_hyperparam
 from ..tencentpretrain.utils.logging import init_logger
-from ..tencentpretrain.utils.optimizers import Adafactor, str2optimizer, str2scheduler
+from ..tencentpretrain.utils.optimizers import Adafactor, apply_grad_clip, str2optimizer, str2scheduler
 from . import misc
 from .xit import XiT
 
@@ -342,7 +342,7 @@ class Actor(_Head):
             self._in_shapes = (tuple(text_emb.shape), None if img_emb is None else tuple(img_emb.shape))
         return logits
 
-    def engine_backward(self, dlogits: torch.Tensor, dp=None, fc1_update=None, input_grads: bool = False):
+    def engine_backward(self, dlogits: torch.Tensor, dp=None, fc1_update=None, input_grads: bool = False, fc1_defer=None):
         """Gradients of sum(dlogits * logits) into the flat gradient buffer (call after engine_forward(save=True)).
         input_grads: -> (d text_emb, d img_emb) in the shapes the forward was given (what the reference's autograd passes on
         to a producer of the features, finetune/ppo.py:214-232); otherwise (None, None)."""
@@ -364,7 +364,8 @@ class Actor(_Head):
             d_text, d_img = (dx0.clone().view(self._in_shapes[0]) if input_grads else None), None
         else:
             d_text, d_img = engine.trunk_backward(ws, P, W, G, text2, img2, dg2, bs, tags, n_img, FEAT, drop=drop,
-                                                  img_shared=shared, dp=dp, fc1_update=fc1_update, input_grads=input_grads)
+                                                  img_shared=shared, dp=dp, fc1_update=fc1_update, input_grads=input_grads,
+                                                  fc1_defer=fc1_defer)
             if input_grads:
                 d_text = d_text.view(self._in_shapes[0])
                 d_img = _shape_img_grad(d_img, self._in_shapes[1], bs, n_img)
@@ -473,7 +474,7 @@ class _TailHead(_Head):
         return value
 
     def engine_backward(self, dvalue: torch.Tensor, dp=None, fc1_update=None, fc1_early: bool = False,
-                        input_grads: bool = False):
+                        input_grads: bool = False, fc1_defer=None):
         """input_grads: -> (d text_emb, d img_emb) in the forward's input shapes: the trunk's input gradients scattered back
         through the `index` gather of finetune/ppo.py:267-271 (a tag picked twice receives the sum); else (None, None)."""
         text_g, img_g, bs, t_out, n_img, drop, drop_t = self._saved
@@ -501,7 +502,7 @@ class _TailHead(_Head):
         else:
             d_text, d_img = engine.trunk_backward(ws, P, W, G, text_g, img_g, dxin, bs, t_out, n_img, FEAT, drop=drop,
                                                   img_shared=False, dp=dp, fc1_update=fc1_update, fc1_early=fc1_early,
-                                                  input_grads=input_grads)
+                                                  input_grads=input_grads, fc1_defer=fc1_defer)
             if input_grads:
                 t_shape, i_shape, index, tags_in, shared_in = self._in_shapes
                 dev = d_text.device
@@ -688,6 +689,7 @@ def build_optimizer(args, model):
                                                   scale_parameter=False, relative_step=False)
         critic_optimizer = str2optimizer[args.optimizer](_grouped(list(model.critic.named_parameters())),
                                                          lr=args.critic_learning_rate, scale_parameter=False, relative_step=False)
+    apply_grad_clip(args, optimizer, critic_optimizer)      # actor and critic each clip their own parameter list
     if args.scheduler in ["constant"]:
         scheduler = str2scheduler[args.scheduler](optimizer)
         critic_scheduler = str2scheduler[args.scheduler](critic_optimizer)
@@ -841,6 +843,18 @@ class _DataParallel:
         self.finish(self.reduce_start(head))
 
 
+def _clipped_fc1_update(optim, head, adam, deferred):
+    """Under gradient-norm clipping, on the stream of `head`: the squared norm of the out_layer.fc1.weight gradient from its factors
+    into the optimizer's slot, norm and coefficient over everything `optim` is about to step, then the fused update the backward
+    held back (engine.trunk_backward(fc1_defer=...)), which scales by that coefficient.  No-op without a deferred update."""
+    if not deferred:
+        return
+    apply, dzo_all, flat_all, K, alpha = deferred[0]
+    engine.fc1_grad_sumsq(head._workspace(dzo_all.buf.device), dzo_all, flat_all, K, alpha, adam.norm_slot)
+    optim.clip_prepare()
+    apply()
+
+
 def update_minibatch(args, model, optimizer, critic_optim, record, dp=None, input_grads: bool = False):
     """The body of one train_model iteration (finetune/ppo.py:518-598) on one stored rollout record:
     actor + critic train forwards, fused PPO loss, actor backward + AdamW, critic backward + AdamW.
@@ -879,26 +893,38 @@ def update_minibatch(args, model, optimizer, critic_optim, record, dp=None, inpu
     # materialised (args.fuse_fc1_update=False restores the separate wgrad + optimizer passes; same bits either way)
     fuse = getattr(args, "fuse_fc1_update", True) and hasattr(optimizer, "external_update") \
         and hasattr(critic_optim, "external_update") and not actor.TRAD          # (`_trad` heads have no 2-GB matrix to fuse)
+    # Gradient-norm clipping (AdamW.set_grad_clip): the fused update needs the coefficient, the coefficient the norm of the gradient
+    # the update never writes -- taken from the gradient's two thin factors (engine.fc1_grad_sumsq) once the rest of backward and
+    # the tail all-reduce are done; the update follows (_clipped_fc1_update), so fc1_early is off.  The Gram products put the rows
+    # of both factors in the GEMM's columns: rows % 4, else the plain route (gradient materialised, in the optimizer's table).
+    clipping = any(getattr(o, "max_grad_norm", None) is not None for o in (optimizer, critic_optim))
+    if clipping and ((bs * tags * dp.world) % 4 or (bs * state.shape[1] * dp.world) % 4):
+        fuse = False
     fa = optimizer.external_update(actor.out_layer.fc1.weight) if fuse else None
     fc = critic_optim.external_update(critic.out_layer.fc1.weight) if fuse else None
+    da = [] if fa is not None and fa.norm_slot is not None else None
+    dc = [] if fc is not None and fc.norm_slot is not None else None
     if probs is not None:        # 'cls': chain d loss / d scores through the expected-label softmax to the class logits
         dscores = ops.cls_scores_bwd(probs, scores.view(-1), dscores.view(-1), torch.empty_like(probs), rows=bs * tags,
                                      C=actor.n_out)
     side.fork_point()
-    ga = actor.engine_backward(dscores, dp, fc1_update=fa, input_grads=input_grads)
+    ga = actor.engine_backward(dscores, dp, fc1_update=fa, input_grads=input_grads, fc1_defer=da)
     wa = dp.reduce_start(actor)            # overlaps the critic's backward
     with side.run():                       # the critic's backward, gradient exchange and optimizer step beside the actor's
         # (its out_layer.fc1 update first, the actor's last: the two HBM-bound passes fall beside the other model's GEMMs)
         gc = critic.engine_backward(dvalue, dp, fc1_update=fc, fc1_early=side.on,
-                                    input_grads=input_grads)
+                                    input_grads=input_grads, fc1_defer=dc)
         wc = dp.reduce_start(critic)
         if side.on:
             dp.finish(wc)
+            _clipped_fc1_update(critic_optim, critic, fc, dc)
             critic_optim.step()
     dp.finish(wa)
+    _clipped_fc1_update(optimizer, actor, fa, da)
     optimizer.step()
     if not side.on:
         dp.finish(wc)
+        _clipped_fc1_update(critic_optim, critic, fc, dc)
         critic_optim.step()
     side.join()
     pm = per.mean(dim=1)
@@ -1159,6 +1185,8 @@ def build_parser():
     parser.add_argument("--synthetic_items", type=int, default=0, help="use SyntheticMovieNet with this many train items")
     parser.add_argument("--synthetic_val_items", type=int, default=16)
     parser.add_argument("--max_cycles", type=int, default=0, help="stop after this many update cycles (0 = run all epochs)")
+    parser.add_argument("--max_grad_norm", type=float, default=0.0,
+                        help="clip the global L2 norm of each optimizer's gradients to this value on the device (0 = off; adamw only)")
     from .features import raw_input_opts
     raw_input_opts(parser)      # --raw_inputs [--image_tower vit_large_14_224] [--fp8_features]: frozen encoder stacks in line
     return parser

@@ -30,7 +30,7 @@ from ..tencentpretrain.model_saver import save_model
 from ..tencentpretrain.opts import adv_opts, finetune_opts, tokenizer_opts
 from ..tencentpretrain.utils.config import load_hyperparam
 from ..tencentpretrain.utils.logging import init_logger
-from ..tencentpretrain.utils.optimizers import str2optimizer, str2scheduler
+from ..tencentpretrain.utils.optimizers import apply_grad_clip, str2optimizer, str2scheduler
 from . import misc
 from .pointwise import get_def_cls, log_sig  # noqa: F401  (identical helpers upstream, :60-74)
 from .ppo import FEAT, SEQ_LEN, Mlp, Reward, _DataParallel, _grouped, _init_normal  # noqa: F401
@@ -166,6 +166,7 @@ def build_optimizer(args, model):
     else:
         optimizer = str2optimizer[args.optimizer](_grouped(list(model.named_parameters())), lr=args.learning_rate,
                                                   scale_parameter=False, relative_step=False)
+    apply_grad_clip(args, optimizer)
     if args.scheduler in ["constant"]:
         scheduler = str2scheduler[args.scheduler](optimizer)
     elif args.scheduler in ["constant_with_warmup"]:
@@ -195,7 +196,9 @@ def train_model(args, model, optimizer, scheduler, text_emb_batch, img_emb_batch
     scores = model.engine_forward(text2, img2, index2, save=True).view(-1)
     loss_acc, dscores = torch.empty(2, device=dev), torch.empty_like(scores)
     ops.pair_hinge(scores, loss_acc, dscores, bs=bs, margin=margin)
-    fuse = getattr(args, "fuse_fc1_update", True) and hasattr(optimizer, "external_update") and not model.TRAD
+    # (gradient-norm clipping takes the unfused route here: the gradient is materialised and sits in the optimizer's table)
+    fuse = getattr(args, "fuse_fc1_update", True) and hasattr(optimizer, "external_update") and not model.TRAD \
+        and getattr(optimizer, "max_grad_norm", None) is None
     fa = optimizer.external_update(model.out_layer.fc1.weight) if fuse else None
     model.engine_backward(dscores, dp, fc1_update=fa)
     dp.finish(dp.reduce_start(model))
@@ -256,6 +259,8 @@ def build_parser():
     parser.add_argument("--synthetic_items", type=int, default=0, help="use SyntheticPairs with this many train items")
     parser.add_argument("--synthetic_val_items", type=int, default=16)
     parser.add_argument("--max_steps", type=int, default=0, help="stop after this many training steps (0 = run all epochs)")
+    parser.add_argument("--max_grad_norm", type=float, default=0.0,
+                        help="clip the global L2 norm of each optimizer's gradients to this value on the device (0 = off; adamw only)")
     from .features import raw_input_opts
     raw_input_opts(parser)      # --raw_inputs [--image_tower vit_large_14_224] [--fp8_features]: frozen encoder stacks in line
     return parser

@@ -244,10 +244,14 @@ def split_planes_multi(table_dev: torch.Tensor, n_chunks: int):
 class AdamArgs:
     """AdamW step fused into a weight-gradient GEMM (lr2_epilogue.adam_*): the GEMM result is the gradient of `p` and is
     consumed on the fly -- m, v, p are updated exactly as lr2_adamw_multi would, the gradient never reaches HBM."""
-    __slots__ = ("p", "m", "v", "lr", "beta1", "beta2", "eps", "weight_decay", "lr_dev")
+    __slots__ = ("p", "m", "v", "lr", "beta1", "beta2", "eps", "weight_decay", "lr_dev", "gscale_dev", "norm_slot")
 
-    def __init__(self, p, m, v, lr, beta1, beta2, eps, weight_decay, lr_dev: Optional[torch.Tensor] = None):
+    def __init__(self, p, m, v, lr, beta1, beta2, eps, weight_decay, lr_dev: Optional[torch.Tensor] = None,
+                 gscale_dev: Optional[torch.Tensor] = None, norm_slot: Optional[torch.Tensor] = None):
         self.lr_dev = lr_dev        # float32[1] device tensor read by the kernel in place of lr (captured steps)
+        # gradient-norm clipping (AdamW.set_grad_clip): float32[1] device tensor the gradient is multiplied by before the update, and
+        # the float64[1] slot the producer of the gradient owes its squared norm to before the coefficient is formed
+        self.gscale_dev, self.norm_slot = gscale_dev, norm_slot
         _chk_f32(p, m, v)
         if not (p.is_contiguous() and m.is_contiguous() and v.is_contiguous() and p.shape == m.shape == v.shape):
             raise ValueError("AdamArgs: p, m, v must be contiguous and of one shape")
@@ -400,6 +404,9 @@ def gemm(a, b, out: Optional[torch.Tensor], M: int, N: int, K: int, *, trans_a=F
         e.adam_lr, e.adam_beta1, e.adam_beta2 = adam.lr, adam.beta1, adam.beta2
         e.adam_eps, e.adam_weight_decay = adam.eps, adam.weight_decay
         e.adam_lr_dev = adam.lr_dev.data_ptr() if adam.lr_dev is not None else None
+        if adam.gscale_dev is not None:
+            _chk_f32(adam.gscale_dev)
+            e.adam_gscale_dev = adam.gscale_dev.data_ptr()
     if colsum is not None:
         # weight-gradient form: colsum[m] = sum_k A[k, m] (the bias gradient) from the same launch (lr2_epilogue.colsum)
         _chk_f32(colsum, colsum_ws)
@@ -1144,6 +1151,55 @@ def adamw_multi(table_dev: torch.Tensor, n_chunks: int, lr: float, beta1: float,
     with _Timed(f"adamw_{n_params}", 0.0, 28.0 * n_params):
         _nat.check(_nat.lib().lr2_adamw_multi(table_dev.data_ptr(), n_chunks, lr, beta1, beta2, eps,
                                               lr_dev.data_ptr() if lr_dev is not None else None, _stream()), "lr2_adamw_multi")
+
+
+def _chk_f64(t: torch.Tensor, what: str):
+    if t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous():
+        raise TypeError(f"{what}: expected a contiguous float64 HIP tensor, got {t.dtype} on {t.device}")
+
+
+def clip_sumsq(table_dev: torch.Tensor, n_chunks: int, partials: torch.Tensor, n_params: int = 0):
+    """partials[i] (float64) = sum of g^2 over chunk i of an AdamW chunk table (lr2_clip_sumsq: fixed order, no atomics)."""
+    _chk_f64(partials, "clip_sumsq")
+    if partials.numel() < n_chunks:
+        raise ValueError("clip_sumsq: one float64 partial per chunk")
+    with _Timed(f"clip_sumsq_{n_params}", 0.0, 4.0 * n_params):
+        _nat.check(_nat.lib().lr2_clip_sumsq(table_dev.data_ptr(), n_chunks, partials.data_ptr(), _stream()), "lr2_clip_sumsq")
+    return partials
+
+
+def clip_gram_dot(a: torch.Tensor, b: torch.Tensor, slot: torch.Tensor, *, n: int, factor: float = 1.0, ld_a: Optional[int] = None,
+                  ld_b: Optional[int] = None):
+    """slot[0] (float64) = factor * sum_ij a[i, j] * b[i, j] over the leading [n, n] of two fp32 matrices (lr2_clip_gram_dot)."""
+    _chk_f32(a, b)
+    _chk_f64(slot, "clip_gram_dot")
+    ld_a, ld_b = ld_a or a.shape[-1], ld_b or b.shape[-1]
+    if a.numel() < (n - 1) * ld_a + n or b.numel() < (n - 1) * ld_b + n or slot.numel() < 1:
+        raise ValueError("clip_gram_dot: a / b must hold n rows of n floats, ld apart; slot one float64")
+    _nat.check(_nat.lib().lr2_clip_gram_dot(a.data_ptr(), b.data_ptr(), n, ld_a, ld_b, factor, slot.data_ptr(), _stream()),
+               "lr2_clip_gram_dot")
+    return slot
+
+
+def clip_coef(slots: torch.Tensor, n: int, max_norm: float, out: torch.Tensor):
+    """out[0] = total_norm = sqrt(slots[0] + ... + slots[n - 1]), out[1] = min(1, max_norm / (total_norm + 1e-6)) (float32, formed in
+    float64): the rule of torch.nn.utils.clip_grad_norm_ (lr2_clip_coef)."""
+    _chk_f64(slots, "clip_coef")
+    _chk_f32(out)
+    if slots.numel() < n or out.numel() < 2 or not out.is_contiguous():
+        raise ValueError("clip_coef: slots must hold n float64 values, out two float32")
+    _nat.check(_nat.lib().lr2_clip_coef(slots.data_ptr(), n, max_norm, out.data_ptr(), _stream()), "lr2_clip_coef")
+    return out
+
+
+def adamw_multi_scaled(table_dev: torch.Tensor, n_chunks: int, lr: float, beta1: float, beta2: float, eps: float,
+                       gscale_dev: torch.Tensor, n_params: int = 0, lr_dev: Optional[torch.Tensor] = None):
+    """adamw_multi on g * gscale_dev[0] (float32 device scalar); the gradients in memory stay as they are."""
+    _chk_f32(gscale_dev)
+    with _Timed(f"adamw_{n_params}", 0.0, 28.0 * n_params):
+        _nat.check(_nat.lib().lr2_adamw_multi_scaled(table_dev.data_ptr(), n_chunks, lr, beta1, beta2, eps,
+                                                     lr_dev.data_ptr() if lr_dev is not None else None, gscale_dev.data_ptr(),
+                                                     _stream()), "lr2_adamw_multi_scaled")
 
 
 def adafactor_multi(tensors_dev: torch.Tensor, tiles_dev: torch.Tensor, n_tiles: int, fin_dev: Optional[torch.Tensor], n_fin: int,

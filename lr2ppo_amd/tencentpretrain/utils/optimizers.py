@@ -40,6 +40,81 @@ class AdamW(Optimizer):
         self._external = set()
         self._external_seen = set()     # ids of parameters ever updated through external_update
         self._lr_dev = None      # per group: float32[1] device tensor the kernels read the learning rate from (use_device_lr)
+        self._max_norm = None    # set_grad_clip
+        self._clip_out = None    # float32[2] on the device: total_norm, coefficient
+        self._clip_slots = None  # float64: [CLIP_EXT slots of externally updated parameters | one partial per chunk]
+        self._clip_ready = False
+        self._ext_slot = {}      # id(p) -> slot of a parameter taken out of the next step() while clipping is on
+
+    CLIP_EXT = 4                 # externally updated parameters per step that can owe a squared norm
+
+    def set_grad_clip(self, max_norm):
+        """Clip the global L2 norm of the gradients to `max_norm` in every later step(); None (or 0) switches it off again.
+        The rule is torch.nn.utils.clip_grad_norm_'s (norm_type 2, error_if_nonfinite False) over exactly the parameters the next
+        step() updates -- those with a gradient -- plus the parameters handed to external_update since the last step: one norm per
+        optimizer, total_norm = sqrt(sum g^2), coef = min(1, max_norm / (total_norm + 1e-6)).  Norm, coefficient and the scaled
+        update are device kernels (lr2_clip_sumsq / lr2_clip_coef / lr2_adamw_multi_scaled): nothing synchronises, a captured graph
+        holds them as they are.  `.total_norm` and `.clip_coef` are float32[1] device tensors, valid after the step.
+        The gradients IN MEMORY STAY UNSCALED: the kernels multiply on the fly, p.grad is what backward wrote.
+        With external_update in play the caller stores the squared norm of that gradient in AdamArgs.norm_slot, calls
+        clip_prepare(), runs the fused kernel (it reads AdamArgs.gscale_dev) and only then step()."""
+        if max_norm is not None:
+            max_norm = float(max_norm)
+            if max_norm != max_norm or max_norm < 0.0 or max_norm == float("inf"):
+                raise ValueError(f"set_grad_clip: max_norm must be a finite number >= 0 or None, got {max_norm}")
+            if max_norm == 0.0:
+                max_norm = None
+        if self._external:
+            raise RuntimeError("set_grad_clip: a fused update is pending (external_update without step())")
+        self._max_norm = max_norm
+        self._clip_ready = False
+
+    @property
+    def max_grad_norm(self):
+        return self._max_norm
+
+    def _clip_state(self):
+        """(slots, out) on the parameters' device.  Sized once for every chunk table this optimizer can build (chunks hold at least
+        2^13 elements), so the slot a fused update was promised never moves."""
+        ps = [p for g in self.param_groups for p in g["params"]]
+        dev = ps[0].device
+        need = self.CLIP_EXT + sum(-(-p.numel() // (1 << 13)) for p in ps)
+        if self._clip_slots is None or self._clip_slots.device != dev or self._clip_slots.numel() < need:
+            if self._ext_slot:
+                raise RuntimeError("AdamW: parameters changed while a fused update is pending")
+            self._clip_slots = torch.zeros(need, dtype=torch.float64, device=dev)
+            self._clip_out = torch.zeros(2, dtype=torch.float32, device=dev)
+        return self._clip_slots, self._clip_out
+
+    @property
+    def total_norm(self):
+        """float32[1] device tensor: the gradient norm the last step() measured (None while clipping is off)."""
+        return None if self._max_norm is None else self._clip_state()[1][0:1]
+
+    @property
+    def clip_coef(self):
+        """float32[1] device tensor: the coefficient the last step() multiplied its gradients by (None while clipping is off)."""
+        return None if self._max_norm is None else self._clip_state()[1][1:2]
+
+    @torch.no_grad()
+    def clip_prepare(self):
+        """Measure the norm and form the coefficient for the next step() (step() calls this itself unless a fused update is
+        pending: its caller must, after filling AdamArgs.norm_slot and before launching the fused kernel)."""
+        if self._max_norm is None:
+            return None
+        slots, out = self._clip_state()
+        off = self.CLIP_EXT
+        for gi, group in enumerate(self.param_groups):
+            table, n, _, n_params = self._table(gi, group)
+            if table is None:
+                continue
+            ops.clip_sumsq(table, n, slots[off:off + n], n_params=n_params)
+            off += n
+        first = self.CLIP_EXT - len(self._ext_slot)
+        if off > first:
+            ops.clip_coef(slots[first:off], off - first, self._max_norm, out)
+        self._clip_ready = True
+        return out[1:2]
 
     def _ensure_state(self, p):
         st = self.state[p]
@@ -77,12 +152,22 @@ class AdamW(Optimizer):
             raise NotImplementedError("external_update needs correct_bias=False (what LR2PPO uses)")
         if p.dtype != torch.float32 or not p.is_cuda or not p.is_contiguous():
             raise RuntimeError("lr2ppo_amd AdamW needs contiguous float32 HIP parameters")
+        gscale = slot = None
+        if self._max_norm is not None:
+            # clipping: the producer of this gradient owes its squared norm (AdamArgs.norm_slot) and scales by the coefficient
+            if id(p) not in self._ext_slot and len(self._ext_slot) >= self.CLIP_EXT:
+                raise RuntimeError(f"AdamW: at most {self.CLIP_EXT} fused updates per step while clipping is on")
+            slots, out = self._clip_state()
+            k = self._ext_slot.setdefault(id(p), len(self._ext_slot))
+            slot, gscale = slots[self.CLIP_EXT - 1 - k:self.CLIP_EXT - k], out[1:2]
+            self._clip_ready = False
         st = self._ensure_state(p)
         st["step"] += 1
         self._external.add(id(p))
         self._external_seen.add(id(p))
         return ops.AdamArgs(p.data, st["exp_avg"], st["exp_avg_sq"], group["lr"], group["betas"][0], group["betas"][1],
-                            group["eps"], group["weight_decay"], lr_dev=self._lr_dev[gi] if self._lr_dev else None)
+                            group["eps"], group["weight_decay"], lr_dev=self._lr_dev[gi] if self._lr_dev else None,
+                            gscale_dev=gscale, norm_slot=slot)
 
     def _table(self, gi: int, group):
         ps = [p for p in group["params"] if p.grad is not None and id(p) not in self._external]
@@ -126,6 +211,12 @@ class AdamW(Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        clip = self._max_norm is not None
+        if clip and not self._clip_ready:
+            if self._ext_slot:
+                raise RuntimeError("AdamW.step: clipping is on and a fused update is pending -- call clip_prepare() after its "
+                                   "squared norm is in AdamArgs.norm_slot and before the fused kernel")
+            self.clip_prepare()
         for gi, group in enumerate(self.param_groups):
             table, n, ps, n_params = self._table(gi, group)
             if table is None:
@@ -143,11 +234,17 @@ class AdamW(Optimizer):
             lr_dev = self._lr_dev[gi] if self._lr_dev else None
             if lr_dev is not None and group["correct_bias"]:
                 raise NotImplementedError("device learning rates need correct_bias=False (what LR2PPO uses)")
-            ops.adamw_multi(table, n, step_size, beta1, beta2, group["eps"], n_params=n_params, lr_dev=lr_dev)
+            if clip:
+                ops.adamw_multi_scaled(table, n, step_size, beta1, beta2, group["eps"], self._clip_out[1:2], n_params=n_params,
+                                       lr_dev=lr_dev)
+            else:
+                ops.adamw_multi(table, n, step_size, beta1, beta2, group["eps"], n_params=n_params, lr_dev=lr_dev)
             ops.mark_params_written(ps)
         if self._external:          # parameters a fused kernel updated since the last step (external_update)
             ops.mark_params_written([p for g_ in self.param_groups for p in g_["params"] if id(p) in self._external])
         self._external.clear()
+        self._ext_slot.clear()
+        self._clip_ready = False
         return loss
 
 
@@ -433,6 +530,24 @@ def get_inverse_square_root_schedule_with_warmup(optimizer, num_warmup_steps, nu
             return 1e-7 / top
         return (top * num_warmup_steps ** 0.5 * step ** -0.5) / top
     return LambdaLR(optimizer, multiplier, last_epoch)
+
+
+def apply_grad_clip(args, *optimizers):
+    """--max_grad_norm X of the training launchers (a flag of this build; 0 = off, the default): every optimizer clips the global L2
+    norm of its own parameter list to X (AdamW.set_grad_clip), as one torch.nn.utils.clip_grad_norm_ call per optimizer would.
+    Adafactor gets no clip and the combination is refused: its update is invariant to the gradient's scale down to eps[0], and it
+    clips its own update (clip_threshold)."""
+    max_norm = float(getattr(args, "max_grad_norm", 0.0) or 0.0)
+    if max_norm != max_norm or max_norm < 0.0:
+        raise ValueError(f"--max_grad_norm must be >= 0 (0 = off), got {max_norm}")
+    if max_norm == 0.0:
+        return
+    for o in optimizers:
+        if not isinstance(o, AdamW):
+            raise ValueError("--max_grad_norm needs --optimizer adamw: Adafactor's update is invariant to the gradient's scale (down "
+                             "to eps[0]) and it clips its own update (clip_threshold), so it gets no gradient-norm clip")
+    for o in optimizers:
+        o.set_grad_clip(max_norm)
 
 
 str2optimizer = {"adamw": AdamW, "adafactor": Adafactor}
