@@ -194,6 +194,18 @@ int lr2_layernorm_bwd(const void* dy, int group, uint64_t group_stride, const vo
                       const void* rstd, const void* resid_grad, void* dx, void* dxm_hi, uint64_t dxm_lo_off, float drop_p,
                       uint64_t drop_seed, uint32_t drop_site, const void* drop_seed_dev, void* partials, int nblocks, int rows, int D,
                       int mode, float eps, void* stream);
+/* lr2_layernorm_fwd for rows of up to 1536 columns (the same kernel with six float4 per lane instead of four; every argument, both
+ * modes and every output form as there; D % 4 == 0, 4 <= D <= 1536).  lr2_layernorm_fwd keeps its refusal of D > 1024.
+ * replaces: the TencentPretrain LayerNorm (tencentpretrain/layers/layer_norm.py:5-21) of a tower wider than 1024 (ViT-H/14: 1280). */
+int lr2_layernorm_fwd_wide(const void* x, const void* gamma, const void* beta, void* out, void* out_hi, uint64_t out_lo_off,
+                           void* mean, void* rstd, int rows, int D, float eps, int mode, int group, uint64_t group_stride,
+                           void* stream);
+/* lr2_layernorm_bwd for rows of up to 1536 columns, every argument as there (partials: [nblocks, 2 D]).
+ * replaces: autograd of the TencentPretrain LayerNorm (tencentpretrain/layers/layer_norm.py:16-21) of a tower wider than 1024. */
+int lr2_layernorm_bwd_wide(const void* dy, int group, uint64_t group_stride, const void* x, const void* gamma, const void* mean,
+                           const void* rstd, const void* resid_grad, void* dx, void* dxm_hi, uint64_t dxm_lo_off, float drop_p,
+                           uint64_t drop_seed, uint32_t drop_site, const void* drop_seed_dev, void* partials, int nblocks, int rows,
+                           int D, int mode, float eps, void* stream);
 /* out[c] (+)= sum_b partials[b*ld + c] for c < cols (deterministic second stage of column reductions; accumulate != 0 adds to out).
  * ld >= cols, else LR2_ERR_SHAPE. */
 int lr2_colsum_partials_finish(const void* partials, int nblocks, int cols, int ld, void* out, int accumulate,
@@ -286,6 +298,30 @@ int lr2_self_attn_bwd(const void* q_hi, const void* k_hi, const void* v_hi, uint
  * lr2_self_attn_fwd / lr2_self_attn_bwd (given o_hi) take the persistent kernels (a pure function of the shape, the CU count and the
  * LR2_ATTN_PERSIST switch; either pointer may be NULL).  No reference counterpart: a test hook of this library's own scheduling. */
 int lr2_self_attn_plan(int batch, int heads, int L, int ld, int ld_do, int* fwd_persistent, int* bwd_persistent);
+
+/* lr2_self_attn_fwd for head widths other than 64: head_dim % 16 == 0, 32 <= head_dim <= 128 (ViT-H/14: 80), every argument as there
+ * with h*head_dim + d in place of h*64 + d.  The width is padded to a multiple of 32 inside the kernel: the padding columns are zeros the
+ * kernel writes, never loaded and never stored.  One key-blocked kernel (64-key blocks, running max / sum) for every L; results are the
+ * same bits from run to run.  head_dim == 64 is accepted (tests set this skeleton against lr2_self_attn_fwd; dispatch never sends it).
+ * LR2_ERR_ARG: a NULL pointer, batch, heads or L not positive, drop_p outside [0, 1).  LR2_ERR_SHAPE: another head_dim, or
+ * lr2_self_attn_fwd's alignment rules.  A refused call launches nothing.
+ * replaces: tencentpretrain/layers/multi_headed_attn.py:61-74 and the mask of encoders/transformer_encoder.py:62-68. */
+int lr2_self_attn_hd_fwd(const void* q_hi, const void* k_hi, const void* v_hi, uint64_t lo_off, int ld, const int64_t* seg,
+                         void* o, void* o_hi, uint64_t o_lo_off, int ld_o, void* lse, float drop_p, uint64_t drop_seed,
+                         uint32_t drop_site, int batch, int heads, int L, int head_dim, float scale, void* stream);
+/* lr2_self_attn_bwd for the head widths of lr2_self_attn_hd_fwd, every argument as there.  Always the recomputing form: a dQ kernel
+ * (two sweeps over 64-key blocks; writes lse_ws and dsum_ws) and a dK / dV kernel (64-query blocks, accumulators in registers); o_hi is
+ * checked as lr2_self_attn_bwd checks it and not read, lse_ws is overwritten.  Errors as lr2_self_attn_hd_fwd.
+ * replaces: autograd of tencentpretrain/layers/multi_headed_attn.py:61-74. */
+int lr2_self_attn_hd_bwd(const void* q_hi, const void* k_hi, const void* v_hi, uint64_t lo_off, int ld, const void* do_hi,
+                         uint64_t do_lo_off, int ld_do, const int64_t* seg, void* dq_hi, void* dk_hi, void* dv_hi,
+                         uint64_t d_lo_off, int ld_d, const void* o_hi, uint64_t o_lo_off, int ld_o, void* lse_ws, void* dsum_ws,
+                         float drop_p, uint64_t drop_seed, uint32_t drop_site, int batch, int heads, int L, int head_dim, float scale,
+                         void* stream);
+/* Diagnostic: counts[0] = accepted lr2_self_attn_hd_fwd calls, counts[1] = accepted lr2_self_attn_hd_bwd calls (host counters, not
+ * synchronised; a refused call moves neither).
+ * replaces: nothing (a test hook, as lr2_xattn_wide_launch_counts). */
+int lr2_self_attn_hd_launch_counts(uint64_t counts[2]);
 
 /* y[r] = dot(x[row(r)], w) + b for r < rows, row(r) = r*row_step + row_off.
  * replaces: self.head = nn.Linear(768, 1) and the last-position select (finetune/ppo.py:228-232,293-295). */

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 LIB_PATH = os.path.join(CSRC, "liblr2ppo_hip.so")
-SOURCES = ["gemm.hip", "gemm256.hip", "gemm256_mx.hip", "gemm256_b1.hip", "gemm256_f16.hip", "gemm256_tn_b1.hip", "norm.hip", "attn.hip", "attn_wide.hip", "selfattn_fwd.hip", "selfattn_bwd.hip", "first_token_attn.hip", "selfattn_mx.hip", "selfattn_mx_blocked.hip","selfattn_b1_train.hip", "selfattn_b1_blocked.hip", "misc.hip", "adafactor.hip", "clip.hip", "fp8.hip", "fp8_train.hip"]
+SOURCES = ["gemm.hip", "gemm256.hip", "gemm256_mx.hip", "gemm256_b1.hip", "gemm256_f16.hip", "gemm256_tn_b1.hip", "norm.hip", "attn.hip", "attn_wide.hip", "selfattn_fwd.hip", "selfattn_bwd.hip", "selfattn_hd.hip", "first_token_attn.hip", "selfattn_mx.hip", "selfattn_mx_blocked.hip","selfattn_b1_train.hip", "selfattn_b1_blocked.hip", "misc.hip", "adafactor.hip", "clip.hip", "fp8.hip", "fp8_train.hip"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "gemm256_ring.h"), os.path.join(CSRC, "fp8_common.h"), os.path.join(CSRC, "selfattn_common.h"), os.path.join(CSRC, "selfattn_b1.h"), os.path.join(INCLUDE, "lr2ppo_hip.h")]
 # flags of single sources, after the common ones (each is explained at the top of its file)
 EXTRA_FLAGS = {"attn_wide.hip": ["-fno-slp-vectorize"]}
@@ -130,6 +130,8 @@ SIGNATURES = {
     "lr2_split_planes_multi": [_P, _I, _P],
     "lr2_layernorm_fwd": [_P, _P, _P, _P, _P, _U64, _P, _P, _I, _I, _F, _I, _I, _U64, _P],
     "lr2_layernorm_bwd": [_P, _I, _U64, _P, _P, _P, _P, _P, _P, _P, _U64, _F, _U64, _U32, _P, _P, _I, _I, _I, _I, _F, _P],
+    "lr2_layernorm_fwd_wide": [_P, _P, _P, _P, _P, _U64, _P, _P, _I, _I, _F, _I, _I, _U64, _P],
+    "lr2_layernorm_bwd_wide": [_P, _I, _U64, _P, _P, _P, _P, _P, _P, _P, _U64, _F, _U64, _U32, _P, _P, _I, _I, _I, _I, _F, _P],
     "lr2_colsum_partials_finish": [_P, _I, _I, _I, _P, _I, _P],
     "lr2_colsum": [_P, _I, _U64, _I, _I, _I, _P, _I, _P, _P],
     "lr2_xattn_fwd": [_P, _P, _P, _P, _I, _U64, _I, _I, _I, _I, _I, _F, _P],
@@ -142,6 +144,10 @@ SIGNATURES = {
     "lr2_self_attn_bwd": [_P, _P, _P, _U64, _I, _P, _U64, _I, _P, _P, _P, _P, _U64, _I, _P, _U64, _I, _P, _P, _F, _U64, _U32, _I,
                           _I, _I, _I, _F, _P],
     "lr2_self_attn_plan": [_I, _I, _I, _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "lr2_self_attn_hd_fwd": [_P, _P, _P, _U64, _I, _P, _P, _P, _U64, _I, _P, _F, _U64, _U32, _I, _I, _I, _I, _F, _P],
+    "lr2_self_attn_hd_bwd": [_P, _P, _P, _U64, _I, _P, _U64, _I, _P, _P, _P, _P, _U64, _I, _P, _U64, _I, _P, _P, _F, _U64, _U32, _I,
+                             _I, _I, _I, _F, _P],
+    "lr2_self_attn_hd_launch_counts": [C.POINTER(C.c_uint64)],
     "lr2_head_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
     "lr2_head_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "lr2_add_period_rows": [_P, _P, _P, _I, _I, _I, _P],

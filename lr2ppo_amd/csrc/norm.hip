@@ -7,12 +7,15 @@
 
 namespace {
 
-constexpr int MAXV = 4;  // float4 per lane -> D <= 1024
+constexpr int MAXV = 4;       // float4 per lane -> D <= 1024
+constexpr int MAXV_WIDE = 6;  // the *_wide entry points: D <= 1536 (ViT-H/14: 1280).  layernorm_fwd_kernel / layernorm_bwd_kernel take the
+                              // count as a template parameter (named MAXV too: inside them it hides the constant above)
 
 __device__ __forceinline__ size_t mapped_row_offset(int r, int group, uint64_t group_stride, int D) {
   return (size_t)(r / group) * group_stride + (size_t)(r % group) * D;
 }
 
+template <int MAXV>
 __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                             const float* __restrict__ beta, float* __restrict__ out,
                                                             bf16_t* __restrict__ out_hi, size_t out_lo_off,
@@ -142,6 +145,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_f16_kernel(const float* __r
 //   mode 0 (nn.LayerNorm, biased variance, eps inside the sqrt):      c2 = sum(g*xhat) / D
 //   mode 1 (TencentPretrain LayerNorm, y = gamma (x - mean) / (std + eps) + beta with the UNBIASED std, layer_norm.py:16-21):
 //           c2 = sum(g*xhat) / ((D - 1) * (1 - eps * rstd)),  rstd = 1 / (std + eps)      [std * rstd = 1 - eps * rstd]
+template <int MAXV>
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restrict__ dy, int group, uint64_t group_stride,
                                                             const float* __restrict__ x, const float* __restrict__ gamma,
                                                             const float* __restrict__ mean_in, const float* __restrict__ rstd_in,
@@ -316,16 +320,32 @@ __global__ __launch_bounds__(256) void colsum_plane_kernel(const bf16_t* __restr
 
 }  // namespace
 
+template <int MV>
+static int layernorm_fwd_impl(const char* what, const void* x, const void* gamma, const void* beta, void* out, void* out_hi,
+                              uint64_t out_lo_off, void* mean, void* rstd, int rows, int D, float eps, int mode, int group,
+                              uint64_t group_stride, void* stream) {
+  if (!x || !gamma || !beta || (!out && !out_hi) || rows <= 0) return LR2_ERR_ARG;
+  if (D % 4 != 0 || D > MV * 256 || D < 4) return LR2_ERR_SHAPE;
+  if (group <= 0) { group = rows; group_stride = 0; }
+  LR2_LAUNCH(layernorm_fwd_kernel<MV>, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const float*)x,
+             (const float*)gamma, (const float*)beta, (float*)out, (bf16_t*)out_hi, (size_t)out_lo_off, (float*)mean,
+             (float*)rstd, rows, D, eps, mode, group, group_stride, (uint8_t*)nullptr, (uint8_t*)nullptr);
+  return lr2_launch_status(what);
+}
+
 extern "C" int lr2_layernorm_fwd(const void* x, const void* gamma, const void* beta, void* out, void* out_hi,
                                  uint64_t out_lo_off, void* mean, void* rstd, int rows, int D, float eps, int mode,
                                  int group, uint64_t group_stride, void* stream) {
-  if (!x || !gamma || !beta || (!out && !out_hi) || rows <= 0) return LR2_ERR_ARG;
-  if (D % 4 != 0 || D > MAXV * 256 || D < 4) return LR2_ERR_SHAPE;
-  if (group <= 0) { group = rows; group_stride = 0; }
-  LR2_LAUNCH(layernorm_fwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const float*)x,
-             (const float*)gamma, (const float*)beta, (float*)out, (bf16_t*)out_hi, (size_t)out_lo_off, (float*)mean,
-             (float*)rstd, rows, D, eps, mode, group, group_stride, (uint8_t*)nullptr, (uint8_t*)nullptr);
-  return lr2_launch_status(__func__);
+  return layernorm_fwd_impl<MAXV>(__func__, x, gamma, beta, out, out_hi, out_lo_off, mean, rstd, rows, D, eps, mode, group, group_stride,
+                                  stream);
+}
+
+// the same for rows of up to 1536 columns (six float4 per lane): lr2_layernorm_fwd keeps its kernel and its refusal of D > 1024
+extern "C" int lr2_layernorm_fwd_wide(const void* x, const void* gamma, const void* beta, void* out, void* out_hi,
+                                      uint64_t out_lo_off, void* mean, void* rstd, int rows, int D, float eps, int mode,
+                                      int group, uint64_t group_stride, void* stream) {
+  return layernorm_fwd_impl<MAXV_WIDE>(__func__, x, gamma, beta, out, out_hi, out_lo_off, mean, rstd, rows, D, eps, mode, group,
+                                       group_stride, stream);
 }
 
 extern "C" int lr2_layernorm_fwd_f16(const void* x, const void* gamma, const void* beta, void* out, void* out_f16, void* mean,
@@ -344,20 +364,21 @@ extern "C" int lr2_layernorm_fwd_mxfp8(const void* x, const void* gamma, const v
   if (!x || !gamma || !beta || !out_q || !out_scales || rows <= 0) return LR2_ERR_ARG;
   if (mode != 0 && mode != 1) return LR2_ERR_ARG;
   if (D % 32 != 0 || D > MAXV * 256 || D < 32) return LR2_ERR_SHAPE;
-  LR2_LAUNCH(layernorm_fwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const float*)x,
+  LR2_LAUNCH(layernorm_fwd_kernel<MAXV>, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const float*)x,
              (const float*)gamma, (const float*)beta, (float*)out, (bf16_t*)nullptr, (size_t)0, (float*)nullptr,
              (float*)nullptr, rows, D, eps, mode, rows, (uint64_t)0, (uint8_t*)out_q, (uint8_t*)out_scales);
   return lr2_launch_status(__func__);
 }
 
-extern "C" int lr2_layernorm_bwd(const void* dy, int group, uint64_t group_stride, const void* x, const void* gamma,
-                                 const void* mean, const void* rstd, const void* resid_grad, void* dx, void* dxm_hi,
-                                 uint64_t dxm_lo_off, float drop_p, uint64_t drop_seed, uint32_t drop_site, const void* drop_seed_dev,
-                                 void* partials, int nblocks, int rows, int D, int mode, float eps, void* stream) {
+template <int MV>
+static int layernorm_bwd_impl(const char* what, const void* dy, int group, uint64_t group_stride, const void* x, const void* gamma,
+                              const void* mean, const void* rstd, const void* resid_grad, void* dx, void* dxm_hi, uint64_t dxm_lo_off,
+                              float drop_p, uint64_t drop_seed, uint32_t drop_site, const void* drop_seed_dev, void* partials,
+                              int nblocks, int rows, int D, int mode, float eps, void* stream) {
   if (!dy || !x || !gamma || !mean || !rstd || !partials || (!dx && !dxm_hi) || rows <= 0 || nblocks <= 0)
     return LR2_ERR_ARG;
   if (mode != 0 && mode != 1) return LR2_ERR_ARG;
-  if (D % 4 != 0 || D > MAXV * 256 || D < 4) return LR2_ERR_SHAPE;
+  if (D % 4 != 0 || D > MV * 256 || D < 4) return LR2_ERR_SHAPE;
   if (group <= 0) { group = rows; group_stride = 0; }
   float scale = 0.f;
   uint32_t thr = 0;
@@ -367,11 +388,29 @@ extern "C" int lr2_layernorm_bwd(const void* dy, int group, uint64_t group_strid
     thr = dropout_threshold(drop_p);
     key = (((uint64_t)drop_site) << 40) ^ (drop_seed * 0x9E3779B97F4A7C15ull);
   }
-  LR2_LAUNCH(layernorm_bwd_kernel, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, (const float*)dy, group, group_stride,
+  LR2_LAUNCH(layernorm_bwd_kernel<MV>, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, (const float*)dy, group, group_stride,
              (const float*)x, (const float*)gamma, (const float*)mean, (const float*)rstd, (const float*)resid_grad,
              (float*)dx, (bf16_t*)dxm_hi, (size_t)dxm_lo_off, scale, thr, key, (const uint64_t*)drop_seed_dev, drop_seed, drop_site,
              (float*)partials, rows, D, mode, eps);
-  return lr2_launch_status(__func__);
+  return lr2_launch_status(what);
+}
+
+extern "C" int lr2_layernorm_bwd(const void* dy, int group, uint64_t group_stride, const void* x, const void* gamma,
+                                 const void* mean, const void* rstd, const void* resid_grad, void* dx, void* dxm_hi,
+                                 uint64_t dxm_lo_off, float drop_p, uint64_t drop_seed, uint32_t drop_site, const void* drop_seed_dev,
+                                 void* partials, int nblocks, int rows, int D, int mode, float eps, void* stream) {
+  return layernorm_bwd_impl<MAXV>(__func__, dy, group, group_stride, x, gamma, mean, rstd, resid_grad, dx, dxm_hi, dxm_lo_off, drop_p,
+                                  drop_seed, drop_site, drop_seed_dev, partials, nblocks, rows, D, mode, eps, stream);
+}
+
+// the same for rows of up to 1536 columns (the block's dgamma / dbeta partials take 48 KiB of LDS instead of 32)
+extern "C" int lr2_layernorm_bwd_wide(const void* dy, int group, uint64_t group_stride, const void* x, const void* gamma,
+                                      const void* mean, const void* rstd, const void* resid_grad, void* dx, void* dxm_hi,
+                                      uint64_t dxm_lo_off, float drop_p, uint64_t drop_seed, uint32_t drop_site,
+                                      const void* drop_seed_dev, void* partials, int nblocks, int rows, int D, int mode, float eps,
+                                      void* stream) {
+  return layernorm_bwd_impl<MAXV_WIDE>(__func__, dy, group, group_stride, x, gamma, mean, rstd, resid_grad, dx, dxm_hi, dxm_lo_off,
+                                       drop_p, drop_seed, drop_site, drop_seed_dev, partials, nblocks, rows, D, mode, eps, stream);
 }
 
 extern "C" int lr2_colsum_partials_finish(const void* partials, int nblocks, int cols, int ld, void* out, int accumulate,

@@ -41,6 +41,7 @@ from ..tencentpretrain.opts import finetune_opts, tokenizer_opts
 _CFG_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "configs")
 VIT_CONFIG = os.path.join(_CFG_DIR, "vit_base_16_224.json")
 VIT_L14_CONFIG = os.path.join(_CFG_DIR, "vit_large_14_224.json")       # BASELINE.json configs[4]: the image-tower swap
+VIT_H14_CONFIG = os.path.join(_CFG_DIR, "vit_huge_14_224.json")        # hidden 1280, 16 heads of 80 columns (csrc/selfattn_hd.hip), 32 layers
 TEXT_CONFIG = os.path.join(_CFG_DIR, "roberta_base.json")
 ROBERTA_VOCAB = 50265      # models/huggingface_gpt2_vocab.txt + the xlm-roberta specials used by roberta_base_en_model
 
@@ -408,7 +409,7 @@ def synthetic_raw_batch(batch: int, tags: int, n_img: int = 16, seq_length: int 
 
 
 # ---- launcher plumbing shared by the three stages' main(): raw items in, features extracted in line ---------------------------
-IMAGE_TOWERS = {"vit_base_16_224": VIT_CONFIG, "vit_large_14_224": VIT_L14_CONFIG}
+IMAGE_TOWERS = {"vit_base_16_224": VIT_CONFIG, "vit_large_14_224": VIT_L14_CONFIG, "vit_huge_14_224": VIT_H14_CONFIG}
 
 
 def finetune_ppo_step(args, fx: FeatureExtractor, model, reward_model, optimizer, critic_optim, enc_optimizer, frames, ids, seg, tgts):
@@ -465,7 +466,9 @@ def raw_input_opts(parser):
     parser.add_argument("--encoder_layers", type=int, default=0, help="override layers_num of both encoder configs (0 = as shipped)")
     parser.add_argument("--image_tower", type=str, default="vit_base_16_224",
                         help="with --raw_inputs: vit_base_16_224 | vit_large_14_224 (BASELINE configs[4]; ends in the 1024 -> "
-                             "visual_feat_dim projection) | path of a TencentPretrain model JSON")
+                             "visual_feat_dim projection) | vit_huge_14_224 (hidden 1280, heads of 80 columns, 1280 -> visual_feat_dim "
+                             "projection; the default and the training precisions, not the --*_features modes) | path of a "
+                             "TencentPretrain model JSON")
     parser.add_argument("--fp8_features", action="store_true",
                         help="with --raw_inputs and frozen encoders: every projection of both stacks as an MX-FP8 product on the "
                              "block-scaled MFMA (FeatureExtractor(precision='mxfp8'); a few per cent from the default features)")

@@ -455,9 +455,10 @@ def layernorm_fwd(x, gamma, beta, out, mean=None, rstd=None, *, rows, D, eps=1e-
             raise ValueError("layernorm_fwd: out_plane excludes out_planes")
         hi = _plane_ptr(out_plane, rows * D, "layernorm_fwd: out_plane")
     with _Timed(f"lnfwd_R{rows}_D{D}", 0.0, (6.0 if out_plane is not None else 8.0) * rows * D):
-        rc = _nat.lib().lr2_layernorm_fwd(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(out), hi, lo_off, _ptr(mean),
-                                          _ptr(rstd), rows, D, eps, mode, group, group_stride, _stream())
-    _nat.check(rc, "lr2_layernorm_fwd")
+        name = "lr2_layernorm_fwd_wide" if D > 1024 else "lr2_layernorm_fwd"        # rows wider than four float4 per lane
+        rc = getattr(_nat.lib(), name)(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(out), hi, lo_off, _ptr(mean),
+                                       _ptr(rstd), rows, D, eps, mode, group, group_stride, _stream())
+    _nat.check(rc, name)
     return out if out is not None else (out_planes if out_planes is not None else out_plane)
 
 
@@ -870,12 +871,13 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dx, partials, dgamma, dbeta, *, rows
         raise ValueError("layernorm_bwd partials workspace too small")
     p, seed, site = (drop.p, drop.seed, drop.site) if drop is not None else (0.0, 0, 0)
     L = _nat.lib()
-    rc = L.lr2_layernorm_bwd(dy.data_ptr(), group, group_stride, x.data_ptr(), gamma.data_ptr(), mean.data_ptr(),
-                             rstd.data_ptr(), _ptr(resid_grad), _ptr(dx),
-                             dx_planes.data_ptr() if dx_planes is not None else None,
-                             dx_planes.lo_off if dx_planes is not None else 0, p, seed, site,
-                             drop.seed_dev_ptr() if drop is not None else None, partials.data_ptr(), nb, rows, D, mode, eps, _stream())
-    _nat.check(rc, "lr2_layernorm_bwd")
+    name = "lr2_layernorm_bwd_wide" if D > 1024 else "lr2_layernorm_bwd"
+    rc = getattr(L, name)(dy.data_ptr(), group, group_stride, x.data_ptr(), gamma.data_ptr(), mean.data_ptr(),
+                          rstd.data_ptr(), _ptr(resid_grad), _ptr(dx),
+                          dx_planes.data_ptr() if dx_planes is not None else None,
+                          dx_planes.lo_off if dx_planes is not None else 0, p, seed, site,
+                          drop.seed_dev_ptr() if drop is not None else None, partials.data_ptr(), nb, rows, D, mode, eps, _stream())
+    _nat.check(rc, name)
     if dbeta.data_ptr() == dgamma.data_ptr() + 4 * D:       # [d gamma | d beta] adjacent (flat gradient buffers): one finishing launch
         _nat.check(L.lr2_colsum_partials_finish(partials.data_ptr(), nb, 2 * D, 2 * D, dgamma.data_ptr(), 0, _stream()), "finish")
         return
@@ -949,10 +951,24 @@ def _qkv_ptrs(qkv, E):
     return base, base + 2 * E, base + 4 * E
 
 
+def _self_attn_hd(head_dim: int) -> bool:
+    """Whether the head-width-general kernels (selfattn_hd.hip) serve this width: multiples of 16 from 32 to 128 except 64, which stays
+    with the 64-column kernels (the same call, the same bits as before); every other width goes to those too and is refused there."""
+    return head_dim != 64 and 32 <= head_dim <= 128 and head_dim % 16 == 0
+
+
+def self_attn_hd_launch_counts():
+    """(forward, backward) calls the head-width-general attention pair has accepted (a test hook: which form a dispatch ran)."""
+    c = (C.c_uint64 * 2)()
+    _nat.check(_nat.lib().lr2_self_attn_hd_launch_counts(c), "lr2_self_attn_hd_launch_counts")
+    return int(c[0]), int(c[1])
+
+
 def self_attn_fwd(qkv: "Planes", seg, o, *, batch, heads, L, head_dim, scale, lse=None, drop: Optional[Drop] = None):
     """Encoder self-attention on the matrix cores.  qkv: Planes [batch*L, 3*heads*head_dim] = [Q | K | V] (what one fused
     QKV GEMM writes); seg: int64 [batch*L]; o: fp32 tensor or Planes [batch*L, heads*head_dim]; lse: optional fp32
-    [batch*heads*L]; drop: dropout on the probabilities."""
+    [batch*heads*L]; drop: dropout on the probabilities.  head_dim 64: lr2_self_attn_fwd; 32 .. 128 in steps of 16 otherwise:
+    lr2_self_attn_hd_fwd."""
     E = heads * head_dim
     if not isinstance(qkv, Planes) or qkv.cols != 3 * E or qkv.rows != batch * L:
         raise TypeError("self_attn_fwd: qkv must be a Planes matrix [batch*L, 3*heads*head_dim]")
@@ -962,11 +978,12 @@ def self_attn_fwd(qkv: "Planes", seg, o, *, batch, heads, L, head_dim, scale, ls
     _chk_f32(None if o_pl else o, lse)
     q, k, v = _qkv_ptrs(qkv, E)
     p, seed, site = (drop.p, drop.seed, drop.site) if drop is not None else (0.0, 0, 0)
+    name = "lr2_self_attn_hd_fwd" if _self_attn_hd(head_dim) else "lr2_self_attn_fwd"
     with _Timed(f"selfattn_B{batch}_H{heads}_L{L}", 4.0 * batch * heads * L * L * head_dim, 16.0 * batch * L * E):
-        _nat.check(_nat.lib().lr2_self_attn_fwd(q, k, v, qkv.lo_off, qkv.cols, seg.data_ptr(),
-                                                None if o_pl else o.data_ptr(), o.data_ptr() if o_pl else None,
-                                                o.lo_off if o_pl else 0, E, _ptr(lse), p, seed, site, batch, heads, L, head_dim,
-                                                scale, _stream()), "lr2_self_attn_fwd")
+        _nat.check(getattr(_nat.lib(), name)(q, k, v, qkv.lo_off, qkv.cols, seg.data_ptr(),
+                                             None if o_pl else o.data_ptr(), o.data_ptr() if o_pl else None,
+                                             o.lo_off if o_pl else 0, E, _ptr(lse), p, seed, site, batch, heads, L, head_dim,
+                                             scale, _stream()), name)
     return o
 
 
@@ -1004,12 +1021,13 @@ def self_attn_bwd(qkv: "Planes", do: "Planes", seg, dqkv: "Planes", lse_ws, dsum
     q, k, v = _qkv_ptrs(qkv, E)
     dq, dk, dv = _qkv_ptrs(dqkv, E)
     p, seed, site = (drop.p, drop.seed, drop.site) if drop is not None else (0.0, 0, 0)
+    name = "lr2_self_attn_hd_bwd" if _self_attn_hd(head_dim) else "lr2_self_attn_bwd"
     with _Timed(f"selfattnbwd_B{batch}_H{heads}_L{L}", 14.0 * batch * heads * L * L * head_dim, 32.0 * batch * L * E):
-        _nat.check(_nat.lib().lr2_self_attn_bwd(q, k, v, qkv.lo_off, qkv.cols, do.data_ptr(), do.lo_off, do.cols, seg.data_ptr(),
-                                                dq, dk, dv, dqkv.lo_off, dqkv.cols, o.data_ptr() if o is not None else None,
-                                                o.lo_off if o is not None else 0, o.cols if o is not None else 0,
-                                                lse_ws.data_ptr(), dsum_ws.data_ptr(), p, seed, site, batch, heads, L, head_dim, scale,
-                                                _stream()), "lr2_self_attn_bwd")
+        _nat.check(getattr(_nat.lib(), name)(q, k, v, qkv.lo_off, qkv.cols, do.data_ptr(), do.lo_off, do.cols, seg.data_ptr(),
+                                             dq, dk, dv, dqkv.lo_off, dqkv.cols, o.data_ptr() if o is not None else None,
+                                             o.lo_off if o is not None else 0, o.cols if o is not None else 0,
+                                             lse_ws.data_ptr(), dsum_ws.data_ptr(), p, seed, site, batch, heads, L, head_dim, scale,
+                                             _stream()), name)
     return dqkv
 
 

@@ -251,6 +251,8 @@ class TransformerEncoder(nn.Module):
     def _forward_infer(self, emb, seg, first_only=False):
         B, L, E = emb.shape
         H, hd = self.heads_num, E // self.heads_num
+        if first_only and hd != 64:                                   # lr2_first_token_attn is built for head width 64: the full
+            return self._forward_infer(emb, seg)[:, 0, :].contiguous()  # last layer, sliced (as forward_bf16 does)
         M = B * L
         if self._ws is None or self._ws.device != emb.device:
             self._ws = engine.Workspace(emb.device)
